@@ -17,7 +17,19 @@ are configs[2]'s 1,000,000 pods) to completion against the
 live cluster, through the whole boundary the cgo caller uses: `value` times
 ks_batch_prepare (pod compile + H2D), ks_batch_submit / ks_batch_wait (every
 round + D2H of the results) and ks_batch_results, pipelined so that compiling
-batch k+1 overlaps running batch k.  Beside it the line reports:
+batch k+1 overlaps running batch k.  A plain run does that and no more: set
+up, W untimed steps, K timed steps, one JSON line.  Its `roofline` needs no run
+of its own: the sweep kernel's VALU issue fraction (its binding resource) from
+the timed steps' HIP-event times and the PMC file measured for this exact
+configuration and kernel source (profiles/pmc/<key>.json, tools/gpu.sh pmc),
+with the measured HBM traffic and its fraction of 8 TB/s beside it.
+
+--dump-outputs DIR also writes what the last timed step returned to its caller
+(one ks_result per pod of the step) as DIR/<field>.npy, float64; the cluster
+and the pod stream are seeded, so two builds run with the same arguments can
+be compared output for output.
+
+With --full the run goes on after the timed steps, and the line also reports:
 
 * value_inputs_resident: the same number of steps with every batch compiled
   and uploaded before the timed region (ks_batch_run only: the device-side
@@ -25,10 +37,6 @@ batch k+1 overlaps running batch k.  Beside it the line reports:
 * latency: per-call wall time of ks_schedule (compile + upload + run +
   results) for 1-, 16- and 256-pod batches (p50 / p99), next to the
   reference's ScheduleOne latency (~560 us per pod per shard, README.adoc:786);
-* roofline: the sweep kernel's VALU issue fraction (its binding resource) from
-  the PMC file measured for this exact configuration and kernel source
-  (profiles/pmc/<key>.json, tools/gpu.sh pmc), with the measured HBM traffic and
-  its fraction of 8 TB/s beside it;
 * cpu_baseline: the C++ oracle (a restatement of upstream kube-scheduler) on a
   bounded prefix of the same stream, on the box's CPU share.
 
@@ -131,9 +139,15 @@ def parse():
                     help="batch: one batch of --batch pods per step; c5: one burst + its event log per step")
     ap.add_argument("--burst", type=int, default=100_000, help="pods per burst (--workload c5)")
     ap.add_argument("--prefill", type=float, default=None, help="max prefill fraction (default 0.5, kwok 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements: the inputs-resident pass, the "
+                         "ks_schedule latencies and the CPU oracle baseline (each can be switched off below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (one ks_result per pod) as DIR/<field>.npy (float64)")
     ap.add_argument("--no-resident", action="store_true",
-                    help="skip the secondary inputs-resident pass (batches compiled + uploaded before timing)")
-    ap.add_argument("--latency-calls", type=int, default=100, help="ks_schedule calls per latency batch size (0: skip)")
+                    help="--full: skip the secondary inputs-resident pass (batches compiled + uploaded before timing)")
+    ap.add_argument("--latency-calls", type=int, default=100,
+                    help="--full: ks_schedule calls per latency batch size (0: skip)")
     ap.add_argument("--cpu-pods", type=int, default=48, help="oracle sample (pods), single thread (~4 s at 1M nodes)")
     ap.add_argument("--cpu-pods-mt", type=int, default=1000, help="oracle sample (pods), multi-thread (~10 s at 1M nodes on 16 threads)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -147,6 +161,8 @@ def parse():
     ap.add_argument("--pmc-dir", default=str(ROOT / "profiles" / "pmc"),
                     help="per-configuration PMC summaries (tools/gpu.sh pmc + tools/pmc_summary.py)")
     a = ap.parse_args()
+    if a.resolve_profile and not a.full:
+        ap.error("--resolve-profile clocks the inputs-resident pass: add --full")
     if a.nodes_per_lane is None:
         a.nodes_per_lane = 2 if a.gpus > 1 else 4
     if a.prefill is None:
@@ -310,11 +326,14 @@ def run_batches(args, kind, sched, world, rank, t_setup):
     st = sched.stats()
     dbg = (C.c_uint64 * 16)()
     sched.lib.ks_debug_counters(sched.ctx, dbg)
-    # secondary: the same number of steps with every batch compiled and
-    # uploaded before the timed region (inputs resident in HBM)
+    last = e2e.pop("last_results")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, args.batch)
+    # secondary (--full): the same number of steps with every batch compiled
+    # and uploaded before the timed region (inputs resident in HBM)
     if args.resolve_profile:
         sched.lib.ks_debug_set_profile(sched.ctx, 1)
-    res = None if args.no_resident else resident(args, kind, sched, world, barrier)
+    res = resident(args, kind, sched, world, barrier) if args.full and not args.no_resident else None
     prof = None
     if args.resolve_profile:
         pr = (C.c_uint64 * 16)()
@@ -329,9 +348,9 @@ def run_batches(args, kind, sched, world, rank, t_setup):
         prof["cycles_per_round"]["total"] = round(sum(int(pr[i]) for i in names) / rounds, 1)
         prof["dirty_recomputes_per_round"] = round(int(pr[10]) / rounds, 2)
         prof["extra_windows_per_round"] = round(int(pr[11]) / rounds, 2)
-    lat = latency(args, kind, sched, world) if args.latency_calls > 0 else None
+    lat = latency(args, kind, sched, world) if args.full and args.latency_calls > 0 else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_pods > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_pods > 0:
         cpu = cpu_baseline(args, nodes, slots, pre, pod_stream(args, kind, args.cpu_pods_mt + args.cpu_pods, 7))
     # one-pod-path filter passes over every node count too: one per pod of the
     # per-pod chain and one per replica run; st covers
@@ -418,12 +437,38 @@ def end_to_end(args, kind, sched, world, barrier):
     if world > 1:
         elapsed = sched.allreduce_max([elapsed])[0]
     return {"pods_timed": n * args.batch, "elapsed": elapsed, "scheduled": scheduled,
+            "last_results": out,  # ks_batch_results of the last timed step (--dump-outputs)
             # pods the sweeps evaluated in the timed steps: one per class of a
             # round's byte-identical pods
             "pods_swept": int(dbg1[2] - dbg0[2]),
             "host_compile_ms_per_step": round(1e3 * compile_s / max(1, n - 1), 3),
             "what": "value: ks_batch_prepare (compile + H2D) + ks_batch_submit/wait (run + D2H) + "
                     "ks_batch_results per step, batch k+1 compiled while batch k runs; fresh pods (seed 7)"}
+
+
+DUMP_FIELDS = ("node_index", "status", "total_score", "feasible", "evaluated", "fail", "flags")
+DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_outputs(path, raw, n):
+    """--dump-outputs: the n ks_result records a step returned to its caller,
+    one float64 array per field (every field is an integer below 2^53, so the
+    conversion is exact).  Steps too large for DUMP_MAX_BYTES are written as a
+    fixed seeded sample of their pods, with the pods' indices beside it."""
+    import numpy as np
+
+    from ksched.framework import results_to_arrays
+
+    r = results_to_arrays(raw, n)
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    row_bytes = 8 * sum(int(np.prod(r.dtype[f].shape, dtype=np.int64)) for f in DUMP_FIELDS)
+    if n * (row_bytes + 8) > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // (row_bytes + 8), replace=False))
+        r = r[idx]
+        np.save(d / "pod_index.npy", idx.astype(np.float64))
+    for f in DUMP_FIELDS:
+        np.save(d / f"{f}.npy", np.ascontiguousarray(r[f], dtype=np.float64))
 
 
 def resident(args, kind, sched, world, barrier):
@@ -523,6 +568,8 @@ def run_c5(args, kind, sched, world, rank, t_setup):
             t_run += dt
             r = results_to_arrays(res, m)
             scheduled += int((r["status"] == 0).sum())
+        if args.dump_outputs and rank == 0 and b == n_bursts - 1:
+            dump_outputs(args.dump_outputs, res, m)
         stream.record(b, res)
         sched.free(batch)
         # the API server's side (log generation, ABI structs) is untimed

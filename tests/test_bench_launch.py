@@ -53,6 +53,39 @@ def test_torchrun_ranks(n):
     check(p, n)
 
 
+def test_dump_outputs_writes_every_result_field_as_float64(tmp_path):
+    # --dump-outputs: one float64 .npy per ks_result field, values exact
+    import importlib.util
+
+    import numpy as np
+
+    from ksched import _abi
+
+    spec = importlib.util.spec_from_file_location("bench", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 37
+    raw = (_abi.KsResult * n)()
+    for i in range(n):
+        raw[i].node_index, raw[i].status, raw[i].total_score = i - 1, i % 3, (1 << 40) + i
+        raw[i].feasible_nodes, raw[i].evaluated_nodes, raw[i].flags = 2 * i, 3 * i, i & 1
+        raw[i].fail_counts[i % 8] = i
+    bench.dump_outputs(tmp_path / "d", raw, n)
+    got = {p.stem: np.load(p) for p in (tmp_path / "d").glob("*.npy")}
+    assert sorted(got) == sorted(bench.DUMP_FIELDS) and all(a.dtype == np.float64 for a in got.values())
+    i = np.arange(n)
+    assert np.array_equal(got["node_index"], i - 1) and np.array_equal(got["status"], i % 3)
+    assert np.array_equal(got["total_score"], (1 << 40) + i) and np.array_equal(got["flags"], i & 1)
+    assert np.array_equal(got["feasible"], 2 * i) and np.array_equal(got["evaluated"], 3 * i)
+    assert got["fail"].shape == (n, 8) and np.array_equal(got["fail"][i, i % 8], i) and got["fail"].sum() == i.sum()
+
+
+def test_resolve_profile_needs_full():
+    p = subprocess.run([sys.executable, "bench.py", "--resolve-profile", "--dry-run"], cwd=ROOT, env=clean_env(),
+                       capture_output=True, text=True, timeout=60)
+    assert p.returncode == 2 and "--full" in p.stderr
+
+
 def test_world_size_mismatch_is_refused():
     env = dict(clean_env(), WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--dry-run"], cwd=ROOT, env=env,

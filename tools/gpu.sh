@@ -62,6 +62,7 @@ case $JOB in
   lines)
     for l in ${1:-c3 c4 c2 kwok kwokbe c5 spread deploy deploydns affinity pct5}; do
       args=$(line_args $l) || exit 1
+      args="--full $args"  # the lines record the secondary measurements too
       timeout -k 10 420 python -u bench.py $args > gpurun_out/bench_${TAG}_$l.json 2> gpurun_out/bench_${TAG}_$l.err
       rc=$?; echo "$l rc=$rc $(summary gpurun_out/bench_${TAG}_$l.json $l)"
       [ $rc -eq 0 ] || { tail -3 gpurun_out/bench_${TAG}_$l.err; exit $rc; }
@@ -123,7 +124,7 @@ PY
       else
         unset KSCHED_LIB_DIR
       fi
-      timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 6 --latency-calls 0 $EXTRA "$@" \
+      timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 6 --latency-calls 0 $EXTRA "$@" \
         > gpurun_out/ab_${TAG}_$v.json 2> gpurun_out/ab_${TAG}_$v.err || { tail -3 gpurun_out/ab_${TAG}_$v.err; exit 1; }
       summary gpurun_out/ab_${TAG}_$v.json $v
     done ;;
@@ -131,7 +132,7 @@ PY
     # one bench configuration on several library builds: VARIANTS="default stamps ..." (lib/<name>)
     for v in ${VARIANTS:-default}; do
       if [ "$v" = default ]; then unset KSCHED_LIB_DIR; else export KSCHED_LIB_DIR=k8s-1m_amd/ksched/lib/$v; fi
-      timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 4 --warmup 1 --latency-calls 0 "$@" \
+      timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 4 --warmup 1 --latency-calls 0 "$@" \
         > gpurun_out/var_${TAG}_$v.json 2> gpurun_out/var_${TAG}_$v.err || { tail -3 gpurun_out/var_${TAG}_$v.err; exit 1; }
       summary gpurun_out/var_${TAG}_$v.json $v
     done ;;
