@@ -249,6 +249,55 @@ struct NumCol {
   uint32_t valid_bit;
 };
 
+// Owner of what a context takes from the HIP runtime: device and pinned
+// buffers, events, streams.  Each is registered where it is created and given
+// back by free_all (ks_close, a failing ks_open): buffers, then events,
+// streams last.  API threads and the batch worker both allocate, hence the
+// mutex.
+class Resources {
+ public:
+  hipError_t dev(void **p, size_t bytes) { return own(hipMalloc(p, bytes), p, DEV); }
+  hipError_t pinned(void **p, size_t bytes) { return own(hipHostMalloc(p, bytes, hipHostMallocDefault), p, PINNED); }
+  hipError_t event(hipEvent_t *e, unsigned flags = hipEventDefault) {
+    return own(hipEventCreateWithFlags(e, flags), (void **)e, EVENT);
+  }
+  // created: the result of the hipStreamCreate... call that made *s
+  hipError_t stream(hipError_t created, hipStream_t *s) { return own(created, (void **)s, STREAM); }
+  // Free one buffer now.  hipFree waits for the whole device: for callers
+  // that have drained every submitted batch.
+  void release(void *p);
+  // A buffer replaced while work in flight may still read it: it stays
+  // allocated until free_all.
+  void retire(void *) {}
+  void free_all();
+
+ private:
+  enum Kind { DEV, PINNED, EVENT, STREAM };  // in the order free_all gives them back
+  struct Held {
+    void *h;
+    Kind kind;
+  };
+  hipError_t own(hipError_t e, void **h, Kind k);
+  static void give_back(const Held &x);
+  std::mutex mu_;
+  std::vector<Held> held_;
+};
+
+// ks_ctx::prof slots (KS_RUN_PROFILE=1: seconds per phase, stderr at ks_close)
+enum ProfSlot {
+  PROF_LOCK_START = 0,  // run_batch waiting for `mu` at the start of a run
+  PROF_ENQUEUE,         // enqueueing rounds
+  PROF_DRAIN,           // drains
+  PROF_RUNS,            // batch runs (a count, not seconds)
+  PROF_LOCK_END,        // waiting for `mu` at the end of a run
+  PROF_UPLOAD,          // the run's own upload of its batch
+  PROF_TIMING,          // timing read-back
+  PROF_PREP_DRAIN,      // ks_batch_prepare: drain wait,
+  PROF_PREP_COMPILE,    // ... compile,
+  PROF_PREP_REST,       // ... acquire / copy / upload
+  PROF_SLOTS
+};
+
 }  // namespace
 
 // ================================================================= context
@@ -369,11 +418,10 @@ struct ks_ctx {
   uint32_t sweep_blocks = 4096, sweep_blocks_ext = 16384;
   // KS_EVENT_PROFILE=1: per event kind, runs / events / seconds of ks_events_apply (stderr at ks_close)
   bool ev_profile = false;
-  // KS_RUN_PROFILE=1: seconds per phase of the batch runs (stderr at ks_close):
-  // [0] waiting for `mu` at run start, [1] enqueueing rounds, [2] drains, [3] runs,
-  // [4] worker runs' wall time, [5] worker idle between submitted runs, [6] worker runs
+  // KS_RUN_PROFILE=1: seconds per phase of the batch runs and of
+  // ks_batch_prepare, by ProfSlot (PhaseTimer; stderr at ks_close)
   bool run_profile = false;
-  double prof[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // [7..9] ks_batch_prepare: drain wait, compile, rest
+  double prof[PROF_SLOTS] = {};
   struct EvProf {
     uint64_t runs = 0, events = 0;
     double s = 0;
@@ -551,10 +599,8 @@ struct ks_ctx {
     std::vector<Pending> d2h_pending;
   };
   Xfer xm;
-  // device buffers replaced while work may be in flight: freed at ks_close
-  // (hipFree synchronises the whole device)
-  std::vector<void *> graveyard;
-  std::vector<void *> pinned_graveyard;
+  // every device / pinned buffer, event and stream of the context and its batches
+  Resources res;
   // batch pool (ks_batch_free returns batches here; buffers are reused)
   std::mutex pool_mu;
   std::vector<ks_batch *> pool;
@@ -615,6 +661,89 @@ constexpr ks_status KS_NEED_DRAIN = (ks_status)0x7F;
 
 namespace {
 
+// `mu` for the batch worker (the start and end of a run): a compile holding
+// it sees mu_wanted and lets the worker in between two pods (compile_yield).
+struct WorkerLock {
+  ks_ctx *c;
+  explicit WorkerLock(ks_ctx *ctx) : c(ctx) {
+    c->mu_wanted.fetch_add(1);
+    c->mu.lock();
+    c->mu_wanted.fetch_sub(1);
+  }
+  ~WorkerLock() { c->mu.unlock(); }
+  WorkerLock(const WorkerLock &) = delete;
+};
+
+// Seconds of one phase added into a profile's accumulator, only while that
+// profile is on: from construction (or the last next()) to next() / stop() /
+// the scope's end.  The clock is not read otherwise.
+class PhaseTimer {
+ public:
+  PhaseTimer(ks_ctx *c, ProfSlot s) : c_(c) { next(s); }      // ks_ctx::prof, KS_RUN_PROFILE
+  PhaseTimer(bool on, double *into) { if (on) start(into); }  // any other accumulator (no next())
+  ~PhaseTimer() { stop(); }
+  PhaseTimer(const PhaseTimer &) = delete;
+  void stop() {
+    if (acc_) *acc_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0_).count();
+    acc_ = nullptr;
+  }
+  void next(ProfSlot s) {
+    stop();
+    if (c_->run_profile) start(&c_->prof[s]);
+  }
+  // the running phase turns out to belong to slot s (its start stays)
+  void rebook(ProfSlot s) {
+    if (acc_) acc_ = &c_->prof[s];
+  }
+
+ private:
+  void start(double *into) {
+    acc_ = into;
+    t0_ = std::chrono::steady_clock::now();
+  }
+  ks_ctx *c_ = nullptr;
+  double *acc_ = nullptr;
+  std::chrono::steady_clock::time_point t0_;
+};
+
+// --------------------------------------------------------------- resources
+
+// e: the result of the call that created *h
+hipError_t Resources::own(hipError_t e, void **h, Kind k) {
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> g(mu_);
+  held_.push_back({*h, k});
+  return e;
+}
+
+void Resources::give_back(const Held &x) {
+  switch (x.kind) {
+    case DEV: (void)hipFree(x.h); break;
+    case PINNED: (void)hipHostFree(x.h); break;
+    case EVENT: (void)hipEventDestroy((hipEvent_t)x.h); break;
+    case STREAM:  // one still busy is left alone: its work may never end
+      if (hipStreamQuery((hipStream_t)x.h) != hipErrorNotReady) (void)hipStreamDestroy((hipStream_t)x.h);
+      break;
+  }
+}
+
+void Resources::release(void *p) {
+  std::lock_guard<std::mutex> g(mu_);
+  auto it = std::find_if(held_.begin(), held_.end(), [p](const Held &x) { return x.h == p && x.kind <= PINNED; });
+  if (it == held_.end()) return;  // null, or not this context's: nothing to give back
+  give_back(*it);
+  held_.erase(it);
+}
+
+void Resources::free_all() {
+  std::lock_guard<std::mutex> g(mu_);
+  // kind by kind, streams last; within a kind the last created first
+  for (int k = DEV; k <= STREAM; ++k)
+    for (auto x = held_.rbegin(); x != held_.rend(); ++x)
+      if (x->kind == k) give_back(*x);
+  held_.clear();
+}
+
 // --------------------------------------------------------------- transfers
 
 inline size_t xround(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -640,7 +769,8 @@ ks_status stall_report(ks_ctx *c, hipStream_t st, const char *what, double ms) {
   // effort: on a hung device the copy may never finish, and the report then
   // says so rather than waiting for it
   std::string flags = "unreadable (the device did not answer the read-back within 2 s)";
-  if (!c->diag_stream && hipStreamCreateWithFlags(&c->diag_stream, hipStreamNonBlocking) != hipSuccess)
+  if (!c->diag_stream &&
+      c->res.stream(hipStreamCreateWithFlags(&c->diag_stream, hipStreamNonBlocking), &c->diag_stream) != hipSuccess)
     c->diag_stream = nullptr;
   hipStream_t d = c->diag_stream;
   if (c->d_flags && c->h_diag && d && hipStreamQuery(d) == hipSuccess) {
@@ -702,22 +832,22 @@ ks_status xfer_sync(ks_ctx *c) { return xfer_sync(c, c->xm); }
 // Start an ABI call's transfers: completes earlier work, then guarantees
 // pin_bytes of staging and dev_bytes of device scratch (each segment is
 // rounded to 256 B: callers include that slack).  Outgrown buffers are
-// retired to the graveyard (freed at ks_close: hipFree would wait for the
-// whole device, including batches running on the other streams).
+// retired (freed at ks_close: a device free would wait for the whole device,
+// including batches running on the other streams).
 ks_status xfer_begin(ks_ctx *c, Xfer &x, size_t pin_bytes, size_t dev_bytes) {
   ks_status st = xfer_sync(c, x);
   if (st) return st;
   if (pin_bytes > x.pin_cap) {
-    if (x.pin) c->pinned_graveyard.push_back(x.pin);
+    c->res.retire(x.pin);
     x.pin = nullptr;
     x.pin_cap = std::max<size_t>(pin_bytes, std::max<size_t>(2 * x.pin_cap, 1 << 20));
-    HIPC(c, hipHostMalloc((void **)&x.pin, x.pin_cap, hipHostMallocDefault));
+    HIPC(c, c->res.pinned((void **)&x.pin, x.pin_cap));
   }
   if (dev_bytes > x.dscr_cap) {
-    if (x.dscr) c->graveyard.push_back(x.dscr);
+    c->res.retire(x.dscr);
     x.dscr = nullptr;
     x.dscr_cap = std::max<size_t>(dev_bytes, std::max<size_t>(2 * x.dscr_cap, 1 << 20));
-    HIPC(c, hipMalloc((void **)&x.dscr, x.dscr_cap));
+    HIPC(c, c->res.dev((void **)&x.dscr, x.dscr_cap));
   }
   return KS_OK;
 }
@@ -755,6 +885,22 @@ ks_status d2h(ks_ctx *c, void *dst, const void *src, size_t bytes) {
   x.d2h_pending.push_back({dst, x.pin_used, bytes});
   x.pin_used += b;
   return KS_OK;
+}
+
+// (index, value) pairs to the device and one kernel over them, then the wait:
+// launch(col, d_idx, d_val, n, more..., stream), e.g. launch_add_u32.
+template <class F, class C, class V, class... More>
+ks_status scatter_pairs(ks_ctx *c, F launch, C *col, const std::vector<uint64_t> &idx, const std::vector<V> &val,
+                        More... more) {
+  if (idx.empty()) return KS_OK;
+  const size_t bytes = idx.size() * (8 + sizeof(V)) + 1024;
+  ks_status st = xfer_begin(c, bytes, bytes);
+  if (st) return st;
+  uint64_t *d_idx = dscratch<uint64_t>(c, idx.size());
+  V *d_val = dscratch<V>(c, val.size());
+  if ((st = h2d(c, d_idx, idx.data(), idx.size() * 8)) || (st = h2d(c, d_val, val.data(), val.size() * sizeof(V)))) return st;
+  HIPC(c, launch(col, d_idx, d_val, (uint32_t)idx.size(), more..., c->stream));
+  return xfer_sync(c);
 }
 
 // --------------------------------------------------------- label encoding
@@ -1508,7 +1654,7 @@ ks_status xres_column(ks_ctx *c, uint32_t name, bool create, uint32_t *out) {
     return c->fail(KS_ERR_UNSUPPORTED, "more than %d extended resource names (%s)", MAX_XRES, c->strs[name].c_str());
   if (!c->d_xalloc) {
     const size_t n = (size_t)MAX_XRES * c->npos;
-    HIPC(c, hipMalloc((void **)&c->d_xalloc, 2 * n * 8));
+    HIPC(c, c->res.dev((void **)&c->d_xalloc, 2 * n * 8));
     HIPC(c, hipMemsetAsync(c->d_xalloc, 0, 2 * n * 8, c->stream));
     c->d_xreq = c->d_xalloc + n;
   }
@@ -1521,15 +1667,7 @@ ks_status xres_column(ks_ctx *c, uint32_t name, bool create, uint32_t *out) {
 // col[idx] = val (add: col[idx] += val) over the extended-resource columns
 // (d_xalloc, then d_xreq at MAX_XRES * npos).
 ks_status xres_scatter(ks_ctx *c, const std::vector<uint64_t> &idx, const std::vector<int64_t> &val, bool add) {
-  if (idx.empty()) return KS_OK;
-  const size_t bytes = idx.size() * 16 + 1024;
-  ks_status st = xfer_begin(c, bytes, bytes);
-  if (st) return st;
-  uint64_t *d_idx = dscratch<uint64_t>(c, idx.size());
-  int64_t *d_val = dscratch<int64_t>(c, val.size());
-  if ((st = h2d(c, d_idx, idx.data(), idx.size() * 8)) || (st = h2d(c, d_val, val.data(), val.size() * 8))) return st;
-  HIPC(c, launch_scatter_i64(c->d_xalloc, d_idx, d_val, (uint32_t)idx.size(), add, c->stream));
-  return xfer_sync(c);
+  return scatter_pairs(c, launch_scatter_i64, c->d_xalloc, idx, val, add);
 }
 
 // PodRequests for the extended resources (resourcehelper.PodRequests: the
@@ -1594,21 +1732,26 @@ ks_status pod_xrequests(ks_ctx *c, const ks_pod &p, bool create, std::vector<std
 
 // --------------------------------------------------------------- devices
 
+// A node's row of the table's label / taint columns as launch_scatter_rows
+// takes it: hard, prefer, lab[LW], num[NNUM].
+constexpr size_t EXT_ROW_WORDS = 2 + LW + NNUM;
+void pack_ext_row(const HostNode &h, uint64_t *e) {
+  e[0] = h.hard;
+  e[1] = h.prefer;
+  for (int k = 0; k < LW; ++k) e[2 + k] = h.lab[k];
+  for (int k = 0; k < NNUM; ++k) e[2 + LW + k] = (uint64_t)h.num[k];
+}
+
 ks_status upload_dirty_ext(ks_ctx *c, Xfer &x) {
   if (c->dirty_ext.empty()) return KS_OK;
   std::sort(c->dirty_ext.begin(), c->dirty_ext.end());
   c->dirty_ext.erase(std::unique(c->dirty_ext.begin(), c->dirty_ext.end()), c->dirty_ext.end());
   const uint32_t n = (uint32_t)c->dirty_ext.size();
   std::vector<uint32_t> pos(n);
-  std::vector<uint64_t> ext((size_t)n * (2 + LW + NNUM));
+  std::vector<uint64_t> ext((size_t)n * EXT_ROW_WORDS);
   for (uint32_t i = 0; i < n; ++i) {
-    const HostNode &h = c->nodes[c->dirty_ext[i]];
     pos[i] = c->slot_pos[c->dirty_ext[i]];
-    uint64_t *e = &ext[(size_t)i * (2 + LW + NNUM)];
-    e[0] = h.hard;
-    e[1] = h.prefer;
-    for (int k = 0; k < LW; ++k) e[2 + k] = h.lab[k];
-    for (int k = 0; k < NNUM; ++k) e[2 + LW + k] = (uint64_t)h.num[k];
+    pack_ext_row(c->nodes[c->dirty_ext[i]], &ext[(size_t)i * EXT_ROW_WORDS]);
   }
   ks_status st = xfer_begin(c, x, n * 4 + ext.size() * 8 + 1024, n * 4 + ext.size() * 8 + 1024);
   if (st) return st;
@@ -1621,10 +1764,16 @@ ks_status upload_dirty_ext(ks_ctx *c, Xfer &x) {
   return KS_OK;
 }
 
+// Device memory of the context, zeroed on its stream, and pinned host memory (Resources).
 template <class T>
 ks_status dalloc(ks_ctx *c, T **p, size_t count) {
-  HIPC(c, hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
+  HIPC(c, c->res.dev((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
   HIPC(c, hipMemsetAsync(*p, 0, std::max<size_t>(count, 1) * sizeof(T), c->stream));
+  return KS_OK;
+}
+template <class T>
+ks_status palloc(ks_ctx *c, T **p, size_t count) {
+  HIPC(c, c->res.pinned((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
   return KS_OK;
 }
 
@@ -1648,6 +1797,7 @@ ks_status term_get(ks_ctx *c, const ks_pod &p, const ks_pod_affinity_term &t, bo
 bool term_valid(const ks_pod_affinity_term &t);
 
 void term_activate(ks_ctx *c, uint32_t tc, int64_t bound_delta, int32_t refs_delta);
+SpreadArgs spread_args(ks_ctx *c);
 
 // Interned (namespace, labels, namespace labels, own affinity terms) of a
 // pod; creates the term classes of its terms (invalid terms are dropped, as
@@ -1798,11 +1948,11 @@ bool class_matches(const ks_ctx *c, const SpreadClass &k, uint32_t set) {
 
 ks_status spread_scratch(ks_ctx *c, uint32_t need) {
   if (need <= c->dom_cap) return KS_OK;
-  // callers have drained every submitted batch (hipFree waits for the device)
+  // callers have drained every submitted batch (a device free waits for the whole device)
   if (ks_status e_ = sync_bounded(c, c->stream, __func__)) return e_;
-  if (c->d_dcnt) (void)hipFree(c->d_dcnt);
-  if (c->d_dflag) (void)hipFree(c->d_dflag);
-  if (c->d_adcnt) (void)hipFree(c->d_adcnt);
+  c->res.release(c->d_dcnt);
+  c->res.release(c->d_dflag);
+  c->res.release(c->d_adcnt);
   c->d_dcnt = c->d_dflag = c->d_adcnt = nullptr;
   const uint32_t cap = std::max<uint32_t>({need, 2 * c->dom_cap, 1024});
   ks_status st;
@@ -2113,7 +2263,7 @@ ks_status term_get(ks_ctx *c, const ks_pod &p, const ks_pod_affinity_term &t, bo
     if (c->d_tcnt) {
       HIPC(c, hipMemcpyAsync(nt, c->d_tcnt, (size_t)c->tcnt_cap * c->npos * 4, hipMemcpyDeviceToDevice, c->stream));
       if (ks_status e_ = sync_bounded(c, c->stream, __func__)) return e_;
-      (void)hipFree(c->d_tcnt);
+      c->res.release(c->d_tcnt);
     }
     c->d_tcnt = nt;
     c->tcnt_cap = cap;
@@ -2497,20 +2647,8 @@ ks_status spread_pods_delta(ks_ctx *c, const uint32_t *sets, const uint32_t *slo
       tdv.push_back(sign * (int32_t)t.second);
     }
   }
-  for (int pass = 0; pass < 2; ++pass) {
-    auto &ix = pass ? tidx : idx;
-    auto &dx = pass ? tdv : dv;
-    if (ix.empty()) continue;
-    const size_t bytes = ix.size() * 12 + 1024;
-    ks_status st = xfer_begin(c, bytes, bytes);
-    if (st) return st;
-    uint64_t *d_idx = dscratch<uint64_t>(c, ix.size());
-    int32_t *d_dv = dscratch<int32_t>(c, dx.size());
-    if ((st = h2d(c, d_idx, ix.data(), ix.size() * 8)) || (st = h2d(c, d_dv, dx.data(), dx.size() * 4))) return st;
-    HIPC(c, launch_add_u32(pass ? c->d_tcnt : c->d_cnt, d_idx, d_dv, (uint32_t)ix.size(), c->stream));
-    if ((st = xfer_sync(c))) return st;
-  }
-  return KS_OK;
+  if (ks_status st = scatter_pairs(c, launch_add_u32, c->d_cnt, idx, dv)) return st;
+  return scatter_pairs(c, launch_add_u32, c->d_tcnt, tidx, tdv);
 }
 
 // Topology-key and class columns of nodes upserted (their labels may have
@@ -2542,17 +2680,8 @@ ks_status spread_nodes_changed(ks_ctx *c, const uint32_t *slots, uint32_t n, boo
   uint32_t need = 0;
   for (auto &k : c->topo) need = std::max(need, k.ndom);
   if ((st = spread_scratch(c, need))) return st;
-  if (!idx.empty()) {
-    const size_t bytes = idx.size() * 12 + 1024;
-    if ((st = xfer_begin(c, bytes, bytes))) return st;
-    uint64_t *d_idx = dscratch<uint64_t>(c, idx.size());
-    uint32_t *d_val = dscratch<uint32_t>(c, val.size());
-    if ((st = h2d(c, d_idx, idx.data(), idx.size() * 8)) || (st = h2d(c, d_val, val.data(), val.size() * 4)))
-      return st;
-    // one index space: topology columns, then (offset by MAX_TOPO_KEYS columns) class columns
-    HIPC(c, launch_scatter_u32(c->d_dom, d_idx, d_val, (uint32_t)idx.size(), c->stream));
-    if ((st = xfer_sync(c))) return st;
-  }
+  // one index space: topology columns, then (offset by MAX_TOPO_KEYS columns) class columns
+  if ((st = scatter_pairs(c, launch_scatter_u32, c->d_dom, idx, val))) return st;
   if (deleted && c->d_tcnt && c->n_terms) {
     idx.clear();
     val.clear();
@@ -2562,16 +2691,7 @@ ks_status spread_nodes_changed(ks_ctx *c, const uint32_t *slots, uint32_t n, boo
           idx.push_back((uint64_t)t * c->npos + c->slot_pos[slots[i]]);
           val.push_back(0);
         }
-    if (!idx.empty()) {
-      const size_t bytes = idx.size() * 12 + 1024;
-      if ((st = xfer_begin(c, bytes, bytes))) return st;
-      uint64_t *d_idx = dscratch<uint64_t>(c, idx.size());
-      uint32_t *d_val = dscratch<uint32_t>(c, val.size());
-      if ((st = h2d(c, d_idx, idx.data(), idx.size() * 8)) || (st = h2d(c, d_val, val.data(), val.size() * 4)))
-        return st;
-      HIPC(c, launch_scatter_u32(c->d_tcnt, d_idx, d_val, (uint32_t)idx.size(), c->stream));
-      if ((st = xfer_sync(c))) return st;
-    }
+    if ((st = scatter_pairs(c, launch_scatter_u32, c->d_tcnt, idx, val))) return st;
   }
   for (uint32_t ti : rebuild)
     if ((st = topo_build(c, ti))) return st;
@@ -2585,7 +2705,7 @@ hipEvent_t get_event(ks_ctx *c) {
     return e;
   }
   hipEvent_t e;
-  if (hipEventCreate(&e) != hipSuccess) return nullptr;
+  if (c->res.event(&e) != hipSuccess) return nullptr;
   return e;
 }
 
@@ -2922,7 +3042,7 @@ ks_status drain_rounds(ks_ctx *c, uint32_t rounds, void *h_res, const void *d_re
 
 // A pooled batch with room for n pods and `words` clause words: device
 // buffers are allocated only when no pooled batch is large enough, and
-// outgrown clause buffers are retired to the graveyard.
+// outgrown clause buffers are retired (a batch in flight may read them).
 ks_status batch_acquire(ks_ctx *c, uint32_t n, size_t words, ks_batch **out) {
   const uint32_t need = std::max<uint32_t>(n, 1);
   ks_batch *b = nullptr;
@@ -2942,27 +3062,28 @@ ks_status batch_acquire(ks_ctx *c, uint32_t n, size_t words, ks_batch **out) {
       std::lock_guard<std::mutex> g(c->pool_mu);
       c->all_batches.push_back(b);
     }
-    HIPC(c, hipMalloc((void **)&b->d_pods, (size_t)need * sizeof(PodDev)));
-    HIPC(c, hipMalloc((void **)&b->d_pinv, (size_t)need * 2 * sizeof(double)));
-    HIPC(c, hipMalloc((void **)&b->d_results, (size_t)need * sizeof(DevResult)));
-    HIPC(c, hipHostMalloc((void **)&b->h_results, (size_t)need * sizeof(DevResult), hipHostMallocDefault));
-    HIPC(c, hipHostMalloc((void **)&b->h_pods, (size_t)need * sizeof(PodDev), hipHostMallocDefault));
-    HIPC(c, hipHostMalloc((void **)&b->h_pinv, (size_t)need * 2 * sizeof(double), hipHostMallocDefault));
-    HIPC(c, hipMalloc((void **)&b->d_cmask, (size_t)need * 8 * CMASK_WORDS));
-    HIPC(c, hipHostMalloc((void **)&b->h_cmask, (size_t)need * 8 * CMASK_WORDS, hipHostMallocDefault));
-    HIPC(c, hipMalloc((void **)&b->d_marks, ((size_t)need + 3) & ~(size_t)3));
-    HIPC(c, hipMalloc((void **)&b->d_cls, (size_t)need * 4));
-    HIPC(c, hipHostMalloc((void **)&b->h_cls, (size_t)need * 4, hipHostMallocDefault));
+    Resources &r = c->res;
+    HIPC(c, r.dev((void **)&b->d_pods, (size_t)need * sizeof(PodDev)));
+    HIPC(c, r.dev((void **)&b->d_pinv, (size_t)need * 2 * sizeof(double)));
+    HIPC(c, r.dev((void **)&b->d_results, (size_t)need * sizeof(DevResult)));
+    HIPC(c, r.pinned((void **)&b->h_results, (size_t)need * sizeof(DevResult)));
+    HIPC(c, r.pinned((void **)&b->h_pods, (size_t)need * sizeof(PodDev)));
+    HIPC(c, r.pinned((void **)&b->h_pinv, (size_t)need * 2 * sizeof(double)));
+    HIPC(c, r.dev((void **)&b->d_cmask, (size_t)need * 8 * CMASK_WORDS));
+    HIPC(c, r.pinned((void **)&b->h_cmask, (size_t)need * 8 * CMASK_WORDS));
+    HIPC(c, r.dev((void **)&b->d_marks, ((size_t)need + 3) & ~(size_t)3));
+    HIPC(c, r.dev((void **)&b->d_cls, (size_t)need * 4));
+    HIPC(c, r.pinned((void **)&b->h_cls, (size_t)need * 4));
     b->cap_pods = need;
   }
   if (words > b->cap_words) {
-    if (b->d_clauses) c->graveyard.push_back(b->d_clauses);
-    if (b->h_clauses) c->pinned_graveyard.push_back(b->h_clauses);
+    c->res.retire(b->d_clauses);
+    c->res.retire(b->h_clauses);
     b->d_clauses = nullptr;
     b->h_clauses = nullptr;
     b->cap_words = std::max<size_t>(words, std::max<size_t>(2 * b->cap_words, 4096));
-    HIPC(c, hipMalloc((void **)&b->d_clauses, b->cap_words * 8));
-    HIPC(c, hipHostMalloc((void **)&b->h_clauses, b->cap_words * 8, hipHostMallocDefault));
+    HIPC(c, c->res.dev((void **)&b->d_clauses, b->cap_words * 8));
+    HIPC(c, c->res.pinned((void **)&b->h_clauses, b->cap_words * 8));
   }
   b->n = 0;
   b->queued = b->done = false;
@@ -3049,7 +3170,7 @@ ks_status replica_run(ks_ctx *c, ks_batch *b, SpreadArgs sa, uint32_t lo, uint32
         (c->run_profile && (st = dalloc(c, &c->d_rk_prof, 4))))
       return st;
     c->rk_tmp_bytes = bytes;
-    HIPC(c, hipHostMalloc((void **)&c->h_rk_ctl, 16, hipHostMallocDefault));
+    if ((st = palloc(c, &c->h_rk_ctl, 4))) return st;
   }
   // static score < 100 x (the weights of LeastAllocated, BalancedAllocation,
   // TaintToleration, NodeAffinity) + 1; ImageLocality adds 0 (no image records)
@@ -3111,14 +3232,7 @@ ks_status late_class_counts(ks_ctx *c, const ks_batch *b) {
   }
   if (idx.empty()) return KS_OK;
   c->stats.late_class_pods += idx.size();
-  const size_t bytes = idx.size() * 12 + 1024;
-  ks_status st = xfer_begin(c, bytes, bytes);
-  if (st) return st;
-  uint64_t *d_idx = dscratch<uint64_t>(c, idx.size());
-  int32_t *d_dv = dscratch<int32_t>(c, dv.size());
-  if ((st = h2d(c, d_idx, idx.data(), idx.size() * 8)) || (st = h2d(c, d_dv, dv.data(), dv.size() * 4))) return st;
-  HIPC(c, launch_add_u32(c->d_cnt, d_idx, d_dv, (uint32_t)idx.size(), c->stream));
-  return xfer_sync(c);
+  return scatter_pairs(c, launch_add_u32, c->d_cnt, idx, dv);
 }
 
 // Run a prepared batch to completion on the scheduler streams; the results
@@ -3144,11 +3258,9 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
   //    the spread path's commits and the round kernels' (class_commit) count them.
   bool classes = false;
   {
-    const auto tw = std::chrono::steady_clock::now();
-    c->mu_wanted.fetch_add(1);
-    std::lock_guard<std::mutex> g(c->mu);
-    c->mu_wanted.fetch_sub(1);
-    if (c->run_profile) c->prof[0] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
+    PhaseTimer wait(c, PROF_LOCK_START);
+    WorkerLock g(c);
+    wait.stop();
     if ((st0 = upload_dirty_ext(c, c->xm))) return st0;
     c->run_t = c->t;
     b->run_seq = ++c->runs_started;
@@ -3173,9 +3285,10 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
       }
     }
   }
-  const auto tu = std::chrono::steady_clock::now();
-  if (!b->uploaded && (st0 = upload_batch(c, b))) return st0;
-  if (c->run_profile) c->prof[5] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tu).count();
+  {
+    PhaseTimer up(c, PROF_UPLOAD);
+    if (!b->uploaded && (st0 = upload_batch(c, b))) return st0;
+  }
   if (classes || b->any_spread)
     HIPC(c, hipMemcpyAsync(b->d_cmask, b->h_cmask, (size_t)std::max<uint32_t>(b->n, 1) * 8 * CMASK_WORDS, hipMemcpyHostToDevice,
                            c->stream));
@@ -3184,39 +3297,11 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
   for (uint32_t lo = 0; lo < b->n;) {
     uint32_t hi = lo;
     if (b->any_spread && b->spread[lo]) {
-      SpreadArgs sa{};
-      {
-        std::lock_guard<std::mutex> g(c->mu);
-        sa.t = c->t;
-        for (uint32_t k = 0; k < c->topo.size(); ++k) sa.ndom[k] = c->topo[k].ndom;
-      }
-      sa.pos_slot = c->d_pos_slot;
-      sa.slot_pos = c->d_slot_pos;
-      sa.npos = c->npos;
+      SpreadArgs sa = spread_args(c);
       sa.pods = b->d_pods;
       sa.clauses = b->d_clauses;
       sa.cmask = b->d_cmask;
-      sa.dom = c->d_dom;
-      sa.cnt = c->d_cnt;
-      sa.xalloc = c->d_xalloc;
-      sa.xreq = c->d_xreq;
-      sa.dcnt = c->d_dcnt;
-      sa.dflag = c->d_dflag;
-      sa.tcnt = c->d_tcnt;
-      sa.adcnt = c->d_adcnt;
-      sa.ipa_raw = c->d_sraw2;
-      sa.dom_cap = c->dom_cap;
-      sa.acc = c->d_acc;
-      sa.st = c->d_sst;
-      sa.raw = c->d_sraw;
-      sa.part = c->d_spart;
       sa.results = b->d_results;
-      sa.counters = c->d_counters;
-      sa.w = Weights{c->cfg.weight_fit, c->cfg.weight_balanced, c->cfg.weight_taint, c->cfg.weight_affinity,
-                     c->cfg.weight_image};
-      sa.w_pts = c->cfg.weight_topology_spread;
-      sa.w_ipa = c->cfg.weight_inter_pod_affinity;
-      sa.evaluated = c->n_present;
       if (c->pct != 100) {
         sa.win = c->d_win;
         sa.win_st = c->d_win_st;
@@ -3276,21 +3361,18 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
         // extra drains per 20,000-pod batch.
         uint32_t rounds = (hi - host_start + c->P - 1) / c->P;
         rounds = std::min<uint32_t>(rounds, 256);
-        const auto te = std::chrono::steady_clock::now();
+        PhaseTimer ph(c, PROF_ENQUEUE);
         for (uint32_t r = 0; r < rounds; ++r) {
           ks_status st = enqueue_round(c, b, r, hi);
           if (st) return st;
         }
-        const auto td = std::chrono::steady_clock::now();
+        ph.next(PROF_DRAIN);
         // results of every pod this pipeline run can resolve, behind its last round
         const uint32_t top = std::min<uint32_t>(hi, host_start + rounds * c->P);
         ks_status st = drain_rounds(c, rounds, b->h_results + host_start, b->d_results + host_start,
                                     (size_t)(top - host_start) * sizeof(DevResult));
         if (st) return st;
-        if (c->run_profile) {
-          c->prof[1] += std::chrono::duration<double>(td - te).count();
-          c->prof[2] += std::chrono::duration<double>(std::chrono::steady_clock::now() - td).count();
-        }
+        ph.stop();
         if (*c->h_start <= host_start) return c->fail(KS_ERR_DEVICE, "no progress in scheduling rounds");
         host_start = *c->h_start;
       }
@@ -3306,11 +3388,9 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
   {
     // NodeInfo.Pods of the nodes this batch bound pods to (later selector
     // classes count them): appended to a log, applied when read
-    const auto tw = std::chrono::steady_clock::now();
-    c->mu_wanted.fetch_add(1);
-    std::lock_guard<std::mutex> g(c->mu);
-    c->mu_wanted.fetch_sub(1);
-    if (c->run_profile) c->prof[4] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
+    PhaseTimer wait(c, PROF_LOCK_END);
+    WorkerLock g(c);
+    wait.stop();
     if (c->pending_bound.size() > (1u << 24)) flush_bound(c);
     for (uint32_t i = 0; i < b->n; ++i)
       if (b->h_results[i].status == KS_POD_SCHEDULED) {
@@ -3324,12 +3404,10 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
     c->runs_done = b->run_seq;
   }
   if (c->timing) {
-    const auto tt = std::chrono::steady_clock::now();
-    ks_status st = collect_timing(c);
-    if (c->run_profile) c->prof[6] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tt).count();
-    if (st) return st;
+    PhaseTimer rd(c, PROF_TIMING);
+    if (ks_status st = collect_timing(c)) return st;
   }
-  c->prof[3] += 1;
+  c->prof[PROF_RUNS] += 1;
   return KS_OK;
 }
 
@@ -3397,6 +3475,8 @@ int32_t ks_abi_version(void) { return KSCHED_ABI_VERSION; }
 
 const char *ks_last_error(const ks_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
+static ks_status open_device(ks_ctx *x, const ks_config *cfg);
+
 ks_status ks_open(const ks_config *cfg, ks_ctx **out) {
   if (!cfg || !out) return KS_ERR_INVALID;
   *out = nullptr;
@@ -3428,7 +3508,20 @@ ks_status ks_open(const ks_config *cfg, ks_ctx **out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return KS_ERR_DEVICE;
   if (cfg->device < 0 || cfg->device >= ndev) return KS_ERR_DEVICE;
   if (hipSetDevice(cfg->device) != hipSuccess) return KS_ERR_DEVICE;
-  ks_ctx *x = c.get();
+  // nothing is allocated on the device before open_device; what it had
+  // allocated when it fails is the context's (Resources) and goes back here
+  if (ks_status st = open_device(c.get(), cfg)) {
+    c->res.free_all();
+    return st;
+  }
+  *out = c.release();
+  return KS_OK;
+}
+
+// ks_open after the configuration's own checks: options, streams, events,
+// geometry and the device tables.
+static ks_status open_device(ks_ctx *x, const ks_config *cfg) {
+  const uint32_t world = x->cfg.world_size;
   {
     // execution options (ks_config; none changes a result)
     // (pass and round caps bounded so the resolve's uint32 products
@@ -3481,15 +3574,16 @@ ks_status ks_open(const ks_config *cfg, ks_ctx **out) {
         else side_mask[i / 32] |= 1u << (i % 32);
         if (i < ncu - nres - nside) main_mask[i / 32] |= 1u << (i % 32);
       }
-      HIPC(x, hipExtStreamCreateWithCUMask(&x->stream, (uint32_t)main_mask.size(), main_mask.data()));
-      HIPC(x, hipExtStreamCreateWithCUMask(&x->rstream, (uint32_t)res_mask.size(), res_mask.data()));
-      HIPC(x, hipExtStreamCreateWithCUMask(&x->sstream, (uint32_t)side_mask.size(), side_mask.data()));
+      const uint32_t words = (uint32_t)main_mask.size();
+      HIPC(x, x->res.stream(hipExtStreamCreateWithCUMask(&x->stream, words, main_mask.data()), &x->stream));
+      HIPC(x, x->res.stream(hipExtStreamCreateWithCUMask(&x->rstream, words, res_mask.data()), &x->rstream));
+      HIPC(x, x->res.stream(hipExtStreamCreateWithCUMask(&x->sstream, words, side_mask.data()), &x->sstream));
     } else {
       int lo = 0, hi = 0;
-      HIPC(x, hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
+      HIPC(x, x->res.stream(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking), &x->stream));
       HIPC(x, hipDeviceGetStreamPriorityRange(&lo, &hi));
-      HIPC(x, hipStreamCreateWithPriority(&x->rstream, hipStreamNonBlocking, hi));
-      HIPC(x, hipStreamCreateWithPriority(&x->sstream, hipStreamNonBlocking, hi));
+      HIPC(x, x->res.stream(hipStreamCreateWithPriority(&x->rstream, hipStreamNonBlocking, hi), &x->rstream));
+      HIPC(x, x->res.stream(hipStreamCreateWithPriority(&x->sstream, hipStreamNonBlocking, hi), &x->sstream));
     }
     x->xm.st = x->stream;
     {  // value_sync = 0: cross-stream hand-offs by event waits instead
@@ -3498,10 +3592,10 @@ ks_status ks_open(const ks_config *cfg, ks_ctx **out) {
       x->value_sync = can != 0 && cfg->value_sync != 0;
     }
     for (int q = 0; q < 2; ++q) {
-      HIPC(x, hipEventCreateWithFlags(&x->ev_sw[q], hipEventDisableTiming));
-      HIPC(x, hipEventCreateWithFlags(&x->ev_res[q], hipEventDisableTiming));
-      HIPC(x, hipEventCreateWithFlags(&x->ev_swept[q], hipEventDisableTiming));
-      HIPC(x, hipEventCreateWithFlags(&x->ev_fixed[q], hipEventDisableTiming));
+      HIPC(x, x->res.event(&x->ev_sw[q], hipEventDisableTiming));
+      HIPC(x, x->res.event(&x->ev_res[q], hipEventDisableTiming));
+      HIPC(x, x->res.event(&x->ev_swept[q], hipEventDisableTiming));
+      HIPC(x, x->res.event(&x->ev_fixed[q], hipEventDisableTiming));
     }
   }
   // shard geometry: contiguous slot ranges; waves rounded to a multiple of 4
@@ -3550,9 +3644,7 @@ ks_status ks_open(const ks_config *cfg, ks_ctx **out) {
       (st = h2d(x, x->d_shards, x->shards.data(), x->S * sizeof(Shard))) ||
       (st = h2d(x, x->d_slot_pos, x->slot_pos.data(), (size_t)x->cap * 4)))
     return st;
-  HIPC(x, hipHostMalloc((void **)&x->h_start, 4, hipHostMallocDefault));
-  HIPC(x, hipHostMalloc((void **)&x->h_seg, 4, hipHostMallocDefault));
-  HIPC(x, hipHostMalloc((void **)&x->h_diag, 64, hipHostMallocDefault));
+  if ((st = palloc(x, &x->h_start, 1)) || (st = palloc(x, &x->h_seg, 1)) || (st = palloc(x, &x->h_diag, 16))) return st;
   // round records: blocks of the widest kernel (npl 2 -> sub = npl / 2)
   uint32_t bmax = 0;
   for (auto &sh : x->shards) bmax = std::max(bmax, blocks_per_shard(sh, x->npl / std::min<uint32_t>(x->npl, 2)));
@@ -3565,9 +3657,7 @@ ks_status ks_open(const ks_config *cfg, ks_ctx **out) {
       (st = dalloc(x, &x->d_frec, 2 * (size_t)x->P * rec_words(x->K) + 2)) ||
       (st = dalloc(x, &x->d_crow, 2 * (size_t)x->P * x->K)) || (st = dalloc(x, &x->d_cext, 2 * (size_t)x->P * x->K)))
     return st;
-  if ((st = xfer_sync(x))) return st;  // all initialisation is stream-ordered
-  *out = c.release();
-  return KS_OK;
+  return xfer_sync(x);  // all initialisation is stream-ordered
 }
 
 void ks_close(ks_ctx *c) {
@@ -3580,8 +3670,9 @@ void ks_close(ks_ctx *c) {
                  "ksched runs: %.0f runs: lock wait %.3f s (at the end %.3f s), enqueue %.3f s, drains %.3f s; "
                  "worker: %.0f runs %.3f s, idle between runs %.3f s; prepare: drain wait %.3f s, compile %.3f s, "
                  "acquire / copy / upload %.3f s; in runs: upload %.3f s, timing read-back %.3f s\n",
-                 c->prof[3], c->prof[0], c->prof[4], c->prof[1], c->prof[2], wp[2], wp[0], wp[1], c->prof[7],
-                 c->prof[8], c->prof[9], c->prof[5], c->prof[6]);
+                 c->prof[PROF_RUNS], c->prof[PROF_LOCK_START], c->prof[PROF_LOCK_END], c->prof[PROF_ENQUEUE],
+                 c->prof[PROF_DRAIN], wp[2], wp[0], wp[1], c->prof[PROF_PREP_DRAIN], c->prof[PROF_PREP_COMPILE],
+                 c->prof[PROF_PREP_REST], c->prof[PROF_UPLOAD], c->prof[PROF_TIMING]);
   if (c->run_profile && c->rk_prof[3]) {
     const uint64_t *h = c->rk_prof;
     const double n = (double)h[3];
@@ -3608,52 +3699,75 @@ void ks_close(ks_ctx *c) {
     return;
   }
   if (c->comm) ncclCommDestroy(c->comm);
-  for (auto &e : c->lg_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->d_lgstage) (void)hipFree(c->d_lgstage);
-  void *bufs[] = {c->t.acpu, c->t.amem, c->t.rcpu, c->t.rmem, c->t.zcpu, c->t.zmem, c->t.apods,
-                  c->t.npods, c->t.hard, c->t.prefer, c->t.lab, c->t.num, c->d_shards, c->d_slot_pos,
-                  c->d_start, c->d_norm, c->d_norm_inv, c->d_pstat, c->d_fix, c->d_brec, c->d_srec, c->d_frec,
-                  c->d_counters, c->d_crow, c->d_cext, c->d_pipe, c->d_carry, c->d_flags, c->d_dom, c->d_dedup,
-                  c->d_pos_slot, c->d_dcnt, c->d_dflag, c->d_acc, c->d_sst, c->d_sraw, c->d_spart,
-                  c->d_xalloc, c->d_tcnt, c->d_adcnt, c->d_sraw2, c->d_rk_keys, c->d_rk_sorted, c->d_rk_val,
-                  c->d_rk_sval, c->d_rk_gstart, c->d_rk_ctl, c->d_rk_tmp, c->d_rk_prof, c->d_win, c->d_win_st};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  if (c->h_start) (void)hipHostFree(c->h_start);
-  if (c->h_seg) (void)hipHostFree(c->h_seg);
-  if (c->h_rk_ctl) (void)hipHostFree(c->h_rk_ctl);
-  if (c->h_diag) (void)hipHostFree(c->h_diag);
-  if (c->xm.pin) (void)hipHostFree(c->xm.pin);
-  if (c->xm.dscr) (void)hipFree(c->xm.dscr);
-  for (void *g : c->graveyard) (void)hipFree(g);
-  for (void *g : c->pinned_graveyard) (void)hipHostFree(g);
-  for (ks_batch *b : c->all_batches) {
-    for (void *p : {(void *)b->d_pods, (void *)b->d_pinv, (void *)b->d_clauses, (void *)b->d_results,
-                    (void *)b->d_cmask, (void *)b->d_marks, (void *)b->d_cls})
-      if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->h_results, (void *)b->h_pods, (void *)b->h_pinv, (void *)b->h_clauses,
-                    (void *)b->h_cmask, (void *)b->h_cls})
-      if (p) (void)hipHostFree(p);
-    delete b;
-  }
-  for (auto &pr : c->ev_sweep) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  for (auto &pr : c->ev_resolve) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  for (auto &pr : c->ev_spread) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  for (auto &r : c->ev_runs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-  for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-  for (int q = 0; q < 2; ++q) {
-    if (c->ev_sw[q]) (void)hipEventDestroy(c->ev_sw[q]);
-    if (c->ev_res[q]) (void)hipEventDestroy(c->ev_res[q]);
-    if (c->ev_swept[q]) (void)hipEventDestroy(c->ev_swept[q]);
-    if (c->ev_fixed[q]) (void)hipEventDestroy(c->ev_fixed[q]);
-  }
-  if (c->diag_stream && hipStreamQuery(c->diag_stream) == hipSuccess) (void)hipStreamDestroy(c->diag_stream);
-  if (c->rstream) (void)hipStreamDestroy(c->rstream);
-  if (c->sstream) (void)hipStreamDestroy(c->sstream);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  c->res.free_all();  // buffers (the batches' too), events, streams last
+  for (ks_batch *b : c->all_batches) delete b;
   delete c;
 }
+
+}  // extern "C"
+
+namespace {
+
+// What one upserted node decides alone: its slot and the exact ranges.
+ks_status check_node_item(const ks_ctx *c, const ks_node &s, uint32_t slot, std::string *why) {
+  char b[64];
+  if (slot >= c->cap) {
+    std::snprintf(b, sizeof b, "slot %u >= capacity %u", slot, c->cap);
+    *why = b;
+    return KS_ERR_NOT_FOUND;
+  }
+  if (s.alloc_milli_cpu < 0 || s.alloc_milli_cpu >= kMaxAlloc || s.alloc_memory < 0 || s.alloc_memory >= kMaxAlloc ||
+      s.alloc_pods < 0 || s.alloc_pods > INT32_MAX - 1) {
+    *why = "node " + str(s.name) + " allocatable outside the exact range";
+    return KS_ERR_RANGE;
+  }
+  // extended / ephemeral columns are only compared (Fit: request >
+  // Allocatable - Requested, exact int64), so any non-negative int64 is
+  // exact; the 2^44 bound is LeastAllocated's (cpu and memory only)
+  for (uint32_t k = 0; k < s.n_extended; ++k)
+    if (s.extended && s.extended[k].value < 0) {
+      *why = "node " + str(s.name) + " extended allocatable negative";
+      return KS_ERR_RANGE;
+    }
+  return KS_OK;
+}
+
+// Node names are unique (metadata.name matchFields resolve a name to one
+// slot): within a call, and against the present nodes, whose name may move
+// off its slot only if that slot's own item is applied by the call too.  One
+// pass over the items of a call that are still accepted (status == nullptr:
+// all of them), in order.
+struct NodeNames {
+  std::unordered_set<uint32_t> in_call;
+  std::unordered_map<std::string, uint32_t> call_names;  // accepted items' names -> slot
+  NodeNames(const uint32_t *slots, uint32_t n, const ks_status *status) {
+    for (uint32_t i = 0; i < n; ++i)
+      if (!status || !status[i]) in_call.insert(slots[i]);
+  }
+  ks_status item(ks_ctx *c, const ks_node &s, const uint32_t slot, std::string *why) {
+    char b[32];
+    const std::string nm = str(s.name);
+    auto ci = call_names.emplace(nm, slot);
+    if (!ci.second && ci.first->second != slot) {
+      std::snprintf(b, sizeof b, "%u and %u", ci.first->second, slot);
+      *why = "node name " + nm + " given to slots " + b;
+      return KS_ERR_INVALID;
+    }
+    const int64_t nid = c->lookup(s.name);
+    if (nid < 0) return KS_OK;
+    auto it = c->name_slot.find((uint32_t)nid);
+    if (it != c->name_slot.end() && it->second != slot && c->nodes[it->second].present && !in_call.count(it->second)) {
+      std::snprintf(b, sizeof b, "%u", it->second);
+      *why = "node name " + nm + " already names slot " + b;
+      return KS_ERR_INVALID;
+    }
+    return KS_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" {
 
 ks_status ks_nodes_upsert(ks_ctx *c, const ks_node *nodes, const uint32_t *slots, uint32_t n) {
   const uint32_t nodes_n = n;
@@ -3670,33 +3784,12 @@ ks_status ks_nodes_upsert(ks_ctx *c, const ks_node *nodes, const uint32_t *slots
   bool grew = false;
   // Validate the whole call first so that a rejected call changes nothing.
   {
-    std::unordered_set<uint32_t> in_call(slots, slots + n);
-    std::unordered_map<std::string, uint32_t> call_names;
+    NodeNames names(slots, n, nullptr);
+    std::string why;
     for (uint32_t i = 0; i < n; ++i) {
-      const ks_node &s = nodes[i];
-      const uint32_t slot = slots[i];
-      if (slot >= c->cap) return c->fail(KS_ERR_NOT_FOUND, "slot %u >= capacity %u", slot, c->cap);
-      if (s.alloc_milli_cpu < 0 || s.alloc_milli_cpu >= kMaxAlloc || s.alloc_memory < 0 ||
-          s.alloc_memory >= kMaxAlloc || s.alloc_pods < 0 || s.alloc_pods > INT32_MAX - 1)
-        return c->fail(KS_ERR_RANGE, "node %s allocatable outside the exact range", str(s.name).c_str());
-      // extended / ephemeral columns are only compared (Fit: request >
-      // Allocatable - Requested, exact int64), so any non-negative int64 is
-      // exact; the 2^44 bound is LeastAllocated's (cpu and memory only)
-      for (uint32_t k = 0; k < s.n_extended; ++k)
-        if (s.extended && s.extended[k].value < 0)
-          return c->fail(KS_ERR_RANGE, "node %s extended allocatable negative", str(s.name).c_str());
-      // node names are unique (metadata.name matchFields resolve a name to one slot)
-      const std::string nm = str(s.name);
-      auto ci = call_names.emplace(nm, slot);
-      if (!ci.second && ci.first->second != slot)
-        return c->fail(KS_ERR_INVALID, "node name %s given to slots %u and %u", nm.c_str(), ci.first->second, slot);
-      const int64_t nid = c->lookup(s.name);
-      if (nid >= 0) {
-        auto it = c->name_slot.find((uint32_t)nid);
-        if (it != c->name_slot.end() && it->second != slot && c->nodes[it->second].present &&
-            !in_call.count(it->second))
-          return c->fail(KS_ERR_INVALID, "node name %s already names slot %u", nm.c_str(), it->second);
-      }
+      ks_status st;
+      if ((st = check_node_item(c, nodes[i], slots[i], &why)) || (st = names.item(c, nodes[i], slots[i], &why)))
+        return c->fail(st, "%s", why.c_str());
     }
   }
   for (uint32_t i = 0; i < n; ++i) {
@@ -3773,18 +3866,14 @@ ks_status ks_nodes_upsert(ks_ctx *c, const ks_node *nodes, const uint32_t *slots
     if (ins.second) {
       pos.push_back(c->slot_pos[slot]);
       core.resize(core.size() + 8);
-      ext.resize(ext.size() + 2 + LW + NNUM);
+      ext.resize(ext.size() + EXT_ROW_WORDS);
       core[(size_t)row * 8 + 3] = is_new ? 1 : 0;  // reset Requested iff absent before this call
     }
     int64_t *cr = &core[(size_t)row * 8];
     cr[0] = h.acpu;
     cr[1] = h.amem;
     cr[2] = h.apods;
-    uint64_t *e = &ext[(size_t)row * (2 + LW + NNUM)];
-    e[0] = h.hard;
-    e[1] = h.prefer;
-    for (int k = 0; k < LW; ++k) e[2 + k] = h.lab[k];
-    for (int k = 0; k < NNUM; ++k) e[2 + LW + k] = (uint64_t)h.num[k];
+    pack_ext_row(h, &ext[(size_t)row * EXT_ROW_WORDS]);
   }
   if (grew) c->dict_version++;
   n = (uint32_t)pos.size();
@@ -3854,60 +3943,16 @@ ks_status ks_nodes_upsert_each(ks_ctx *c, const ks_node *nodes, const uint32_t *
   std::string first_err;
   std::vector<std::string> why(n);
   // Pass 1: what each item decides alone (slot, ranges).
-  for (uint32_t i = 0; i < n; ++i) {
-    const ks_node &s = nodes[i];
-    const uint32_t slot = slots[i];
-    ks_status st = KS_OK;
-    const std::string nm = str(s.name);
-    if (slot >= c->cap) {
-      st = KS_ERR_NOT_FOUND;
-      why[i] = "slot " + std::to_string(slot) + " >= capacity";
-    } else if (s.alloc_milli_cpu < 0 || s.alloc_milli_cpu >= kMaxAlloc || s.alloc_memory < 0 ||
-               s.alloc_memory >= kMaxAlloc || s.alloc_pods < 0 || s.alloc_pods > INT32_MAX - 1) {
-      st = KS_ERR_RANGE;
-      why[i] = "node " + nm + " allocatable outside the exact range";
-    } else {
-      for (uint32_t k = 0; k < s.n_extended && !st; ++k)
-        if (s.extended && s.extended[k].value < 0) {
-          st = KS_ERR_RANGE;
-          why[i] = "node " + nm + " extended allocatable negative";
-        }
-    }
-    status[i] = st;
-  }
+  for (uint32_t i = 0; i < n; ++i) status[i] = check_node_item(c, nodes[i], slots[i], &why[i]);
   // Pass 2: node-name uniqueness, judged against the items still accepted.
   // A name may move off a slot only if that slot's own item is applied too,
   // so a rejection can reject another item: repeat until nothing changes
   // (rejections only shrink the accepted set, so this ends).
   for (bool changed = true; changed;) {
     changed = false;
-    std::unordered_set<uint32_t> in_call;
+    NodeNames names(slots, n, status);
     for (uint32_t i = 0; i < n; ++i)
-      if (!status[i]) in_call.insert(slots[i]);
-    std::unordered_map<std::string, uint32_t> call_names;  // accepted items' names -> slot
-    for (uint32_t i = 0; i < n; ++i) {
-      if (status[i]) continue;
-      const ks_node &s = nodes[i];
-      const uint32_t slot = slots[i];
-      const std::string nm = str(s.name);
-      auto ci = call_names.emplace(nm, slot);
-      if (!ci.second && ci.first->second != slot) {
-        status[i] = KS_ERR_INVALID;
-        why[i] = "node name " + nm + " given to two slots";
-        changed = true;
-        continue;
-      }
-      const int64_t nid = c->lookup(s.name);
-      if (nid >= 0) {
-        auto it = c->name_slot.find((uint32_t)nid);
-        if (it != c->name_slot.end() && it->second != slot && c->nodes[it->second].present &&
-            !in_call.count(it->second)) {
-          status[i] = KS_ERR_INVALID;
-          why[i] = "node name " + nm + " already names another slot";
-          changed = true;
-        }
-      }
-    }
+      if (!status[i] && (status[i] = names.item(c, nodes[i], slots[i], &why[i]))) changed = true;
   }
   for (uint32_t i = 0; i < n; ++i) {
     if (status[i]) {
@@ -4181,17 +4226,18 @@ ks_status ks_events_apply(ks_ctx *c, const ks_event *ev, uint32_t n) {
     }
     const uint32_t m = j - i;
     ks_status st = KS_OK;
-    const auto t0 = std::chrono::steady_clock::now();
-    switch (kind) {
-      case KS_EV_POD_ADD: st = pods_delta(c, pods.data(), slots.data(), m, +1); break;
-      case KS_EV_POD_REMOVE: st = pods_delta(c, pods.data(), slots.data(), m, -1); break;
-      case KS_EV_NODE_UPSERT: st = ks_nodes_upsert(c, nodes.data(), slots.data(), m); break;
-      default: st = ks_nodes_delete(c, slots.data(), m); break;
+    {
+      PhaseTimer tm(c->ev_profile, &c->ev_prof[kind].s);
+      switch (kind) {
+        case KS_EV_POD_ADD: st = pods_delta(c, pods.data(), slots.data(), m, +1); break;
+        case KS_EV_POD_REMOVE: st = pods_delta(c, pods.data(), slots.data(), m, -1); break;
+        case KS_EV_NODE_UPSERT: st = ks_nodes_upsert(c, nodes.data(), slots.data(), m); break;
+        default: st = ks_nodes_delete(c, slots.data(), m); break;
+      }
     }
     if (c->ev_profile) {
       c->ev_prof[kind].runs++;
       c->ev_prof[kind].events += m;
-      c->ev_prof[kind].s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
     if (st) return st;
     i = j;
@@ -4279,8 +4325,7 @@ ks_status ks_batch_prepare(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_batch *
   }
   bool drained = !any_solo;
   if (!drained) drained = c->runq->idle();
-  const auto tp0 = std::chrono::steady_clock::now();
-  auto tp1 = tp0;
+  PhaseTimer ph(c, PROF_PREP_COMPILE);
   std::vector<uint32_t> set_ids(n), refs, term_refs;
   for (;;) {
     {
@@ -4318,9 +4363,10 @@ ks_status ks_batch_prepare(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_batch *
     if (st != KS_NEED_DRAIN) break;
     drain_async(c);
     drained = true;
-    tp1 = std::chrono::steady_clock::now();
+    ph.rebook(PROF_PREP_DRAIN);  // drain wait: everything up to the end of the drain, the refused compile included
+    ph.next(PROF_PREP_COMPILE);
   }
-  const auto tp2 = std::chrono::steady_clock::now();
+  ph.next(PROF_PREP_REST);
   if (norm) ext = true;
   if (cl.w.empty()) cl.w.push_back(0);
   ks_batch *b = nullptr;
@@ -4375,11 +4421,6 @@ ks_status ks_batch_prepare(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_batch *
       batch_release(c, b);
       return st;
     }
-  }
-  if (c->run_profile) {
-    c->prof[7] += std::chrono::duration<double>(tp1 - tp0).count();
-    c->prof[8] += std::chrono::duration<double>(tp2 - tp1).count();
-    c->prof[9] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp2).count();
   }
   *out = b;
   return KS_OK;
@@ -4658,8 +4699,8 @@ ks_status ks_comm_init_local(ks_ctx *const *ctxs, uint32_t n) {
     ks_ctx *c = ctxs[r];
     if (ks_status dst_ = drain_async(c)) return dst_;
     HIPC(c, hipSetDevice(c->cfg.device));
-    for (auto &e : c->lg_ev) HIPC(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPC(c, hipMalloc((void **)&c->d_lgstage, 4 * (size_t)MAX_P * sizeof(uint32_t)));
+    for (auto &e : c->lg_ev) HIPC(c, c->res.event(&e, hipEventDisableTiming));
+    HIPC(c, c->res.dev((void **)&c->d_lgstage, 4 * (size_t)MAX_P * sizeof(uint32_t)));
     c->lgroup = g;
   }
   return KS_OK;

@@ -314,3 +314,59 @@ def test_upsert_each_name_moves_only_with_its_slot():
         assert rc != 0 and list(status)[:2] == [5, 1] and status[2] == 0, list(status)
         st = s.node_states([0, 1, 2])
         assert all(x.pod_count == 0 for x in st), "the valid item was not applied"
+
+
+def _free_device_bytes():
+    # the HIP runtime libksched itself loaded (no second runtime in the process)
+    _abi.ksched_lib()
+    with open("/proc/self/maps") as f:
+        path = next(ln.split()[-1] for ln in f if "libamdhip64.so" in ln)
+    hip = C.CDLL(path)
+    free, total = C.c_size_t(), C.c_size_t()
+    assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+    return free.value
+
+
+def test_context_gives_back_what_it_took():
+    # Five open .. close cycles that each touch every lazily allocated group of
+    # a context; free device memory after cycle 5 must not be below that after
+    # cycle 1 (which absorbs the runtime's one-time allocations) by as much as
+    # the six int64 resource columns of one context's node table, a lower
+    # bound on what one leaked context holds.
+    from ksched.objects import (Container, LabelSelector, Node, Pod, PodAffinityTerm,
+                                TopologySpreadConstraint)
+
+    cap = 100_000
+    bound = 6 * 8 * cap
+    Gi = 1 << 30
+    sel = LabelSelector({"app": "a"})
+    nodes = [Node(f"n{i}", {"cpu": 32000, "memory": 256 * Gi, "pods": 110}, {"zone": f"z{i % 4}"}, [], False,
+                  extended={"example.com/gpu": 4} if i == 0 else {}) for i in range(16)]
+    plain = [pod(f"p{i}", cpu=100 + i) for i in range(300)]
+    free_after = []
+    for cycle in range(5):
+        a = Arena()
+        with Scheduler(cap, device=0, pods_per_round=128) as s:
+            s.set_timing(True)  # event pool
+            s.upsert_nodes(nodes)  # xres columns (node side)
+            res = s.schedule_pods(plain[:8])  # resource-only batch
+            res += s.schedule_pods([
+                Pod("spread", labels={"app": "a"},  # spread columns
+                    topology_spread=[TopologySpreadConstraint(1, "zone", "DoNotSchedule", sel)]),
+                Pod("gpu", containers=[Container({"cpu": 100, "example.com/gpu": 1})]),  # xres columns
+                Pod("aff", labels={"app": "a"}, affinity_terms=[PodAffinityTerm("zone", sel)])])  # term columns
+            assert not any(isinstance(r, Exception) for r in res), res
+            # a pooled batch of 10, then one of 300 that outgrows it; the
+            # per-plugin dump outgrows the staging buffers
+            for n in (10, 300):
+                pa, _ = pods_array(plain[:n], a)
+                s.free(s.prepare(pa, n))
+            s.plugin_scores(plain[0])
+            free_open = _free_device_bytes()
+        free_after.append(_free_device_bytes())
+        # the measure sees a context: an open one holds at least the bound
+        assert free_after[-1] - free_open >= bound, (free_open, free_after)
+    drift = free_after[0] - free_after[4]
+    print(f"free device memory after cycles 1..5: {free_after}; drift {drift} B (bound {bound} B); "
+          f"an open context held {free_after[-1] - free_open} B")
+    assert drift < bound, free_after

@@ -103,7 +103,7 @@ def main():
         kernels[name]["avg_ms_under_pmc"] = sum(ds) / len(ds) if ds else None
     out = {"tag": a.tag, "key": key, "kernel_src": kernel_src_hash(), "evals_per_launch": evals,
            "workload": line["config"]["workload"],
-           "source": f"rocprofv3 --pmc passes (tools/gpu.sh pmc), {a.dir}", "kernels": kernels}
+           "source": f"rocprofv3 --pmc passes (tools/gpu.sh pmc {a.tag})", "kernels": kernels}
     sweep = {n: v for n, v in kernels.items() if SWEEP in n}
     if sweep:
         name, s = max(sweep.items(), key=lambda kv: kv[1].get("dispatches", 0))
