@@ -610,6 +610,15 @@ ks_status ks_reset_stats(ks_ctx *ctx);
  * (one class of identical request-less pods).  (The instrumented stamps builds,
  * k8s-1m_amd/csrc/ksched_instr.hpp, put phase cycle sums in [8..15].) */
 ks_status ks_debug_counters(ks_ctx *ctx, uint64_t out[16]);
+/* Geometry of the most recent sweep launch of one kind (ext 0: resource-only,
+ * else label / taint; the FIX re-sweeps of flagged pods are not recorded), so
+ * a test knows which kernel and which grid it ran: out[0] launches of that
+ * kind since ks_open, [1] the kernel's nodes per lane, [2] its label-word
+ * variant (1, 2 or 4 words per node; 0 for resource-only), [3] kernel waves
+ * per layout wave (nodes_per_lane / [1]), [4] blocks per shard, [5] pod
+ * groups, [6] pods per group, [7] 0.  Host only; all zero before the first
+ * launch of that kind. */
+ks_status ks_debug_sweep_geometry(ks_ctx *ctx, int32_t ext, uint64_t out[8]);
 /* Diagnostics of the parallel commit: with the profile
  * on, every round accumulates s_memtime cycles per phase: out[0] stage,
  * [1] gather barrier, [2] proposals, [3] wave 0's row DMA issue, [4] chunk

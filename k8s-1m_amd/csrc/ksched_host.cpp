@@ -416,6 +416,9 @@ struct ks_ctx {
   // (C4 sweep 1.117 -> 1.102 ms; 4096 measured 2 % slower than 8192, 32768
   // no better: profiles/r3/sweep_blocks_ab/c4_*): sweep_pairs / sweep_pairs_ext
   uint32_t sweep_blocks = 4096, sweep_blocks_ext = 16384;
+  // ks_debug_sweep_geometry: the last non-FIX sweep launch of each kind
+  // ([0] resource-only, [1] label / taint), as enqueue_round issued it
+  uint64_t sweep_geom[2][8] = {};
   // KS_EVENT_PROFILE=1: per event kind, runs / events / seconds of ks_events_apply (stderr at ks_close)
   bool ev_profile = false;
   // KS_RUN_PROFILE=1: seconds per phase of the batch runs and of
@@ -2948,6 +2951,16 @@ ks_status enqueue_round(ks_ctx *c, ks_batch *b, uint32_t k, uint32_t end) {
   if (early) HIPC(c, hipMemsetAsync(c->d_pstat, 0, (size_t)c->P * sizeof(PodStat), c->stream));
   HIPC(c, launch_sweep(a, b->ext, bmax, groups, nloc, c->stream));
   ++c->sweeps_issued;
+  {
+    uint64_t *g = c->sweep_geom[b->ext ? 1 : 0];
+    ++g[0];
+    g[1] = knpl;
+    g[2] = b->ext ? sweep_label_words(knpl, a.t.lw) : 0;
+    g[3] = sub;
+    g[4] = bmax;
+    g[5] = groups;
+    g[6] = pg;
+  }
   if (tm) {
     HIPC(c, hipEventRecord(e1, c->stream));
     c->ev_sweep.emplace_back(e0, e1);
@@ -4822,6 +4835,13 @@ ks_status ks_debug_counters(ks_ctx *c, uint64_t out[16]) {
     return st;
   out[5] = c->label_resets;
   out[6] = c->taint_rebuilds;
+  return KS_OK;
+}
+
+ks_status ks_debug_sweep_geometry(ks_ctx *c, int32_t ext, uint64_t out[8]) {
+  if (!c || !out) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  std::memcpy(out, c->sweep_geom[ext ? 1 : 0], sizeof c->sweep_geom[0]);
   return KS_OK;
 }
 

@@ -155,7 +155,10 @@ __device__ __forceinline__ void preferred_raw_n(const PodDev &p, const uint64_t 
 // from inv = RN(1 / max) (0 for max == 0, giving 0): the product is within
 // 2^-44 of the quotient (<= 100), whose fractional part is 0 or >= 2^-25, so
 // 2^-40 lifts exact quotients above the rounding error without reaching the
-// next integer: truncation is the exact floor.
+// next integer: truncation is the exact floor.  Checked on the
+// host against integer division (tools/norm_check.cpp, tests/test_exact_arith.py)
+// for every 0 <= raw <= max <= 16384 and for the top corner max in
+// [2^25 - 4096, 2^25), raw in [max - 4096, max].
 constexpr double NORM_EPS = 0x1p-40;
 __device__ __forceinline__ uint32_t normalize_inv(uint32_t raw, double inv) {
   return (uint32_t)__builtin_fma((double)(100u * raw), inv, NORM_EPS);
@@ -1184,7 +1187,7 @@ hipError_t launch_sweep(const RoundArgs &a, bool ext, uint32_t nblocks, uint32_t
   dim3 g(nblocks, ngroups, nshards);
   if (ext) {
     // label words in use (dictionary size): 1, 2 or 4 words per node are read
-    const int lwu = a.t.lw <= 1 ? 1 : a.t.lw <= 2 ? 2 : 4;
+    const uint32_t lwu = sweep_label_words(a.npl, a.t.lw);
     if (a.npl == 2) {
       if (lwu == 1) sweep_kernel<2, true, 1><<<g, SWEEP_THREADS, 0, st>>>(a);
       else if (lwu == 2) sweep_kernel<2, true, 2><<<g, SWEEP_THREADS, 0, st>>>(a);

@@ -210,6 +210,13 @@ hipError_t launch_scatter_i64(int64_t *col, const uint64_t *idx, const int64_t *
                               hipStream_t st);
 
 hipError_t launch_norm_check(const RoundArgs &a, hipStream_t st);
+// Label-word variant of the label / taint sweep (sweep_kernel's LWU): the
+// words per node it reads, by the dictionary's width.  NPL 8 is compiled for
+// 4 words only.  launch_sweep dispatches by it and ks_debug_sweep_geometry
+// reports it.
+inline uint32_t sweep_label_words(uint32_t knpl, uint32_t lw) {
+  return knpl == 8 ? 4u : lw <= 1 ? 1u : lw <= 2 ? 2u : 4u;
+}
 hipError_t launch_sweep(const RoundArgs &a, bool ext, uint32_t nblocks, uint32_t ngroups, uint32_t nshards,
                         hipStream_t st);
 hipError_t launch_merge(const RoundArgs &a, uint32_t nshards, hipStream_t st);

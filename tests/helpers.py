@@ -35,6 +35,38 @@ def scores_array(scores):
                     dtype=np.int64)
 
 
+def oracle_keys(o, pod_ptr):
+    """The oracle's packed keys ((TotalScore + 1) << 32 | ~slot) of the pod's
+    feasible nodes against the current state, descending, and their count."""
+    sc = scores_array(o.plugin_scores(pod_ptr))
+    feas = np.nonzero(sc[:, 0] == -1)[0]
+    keys = ((sc[feas, -1].astype(np.uint64) + np.uint64(1)) << np.uint64(32)) | (
+        np.uint64(0xFFFFFFFF) - feas.astype(np.uint64))
+    return np.sort(keys)[::-1], len(feas)
+
+
+def assert_round_records(s, want, r, m, K):
+    """ks_debug_round_record of pods 0..m of a batch that one round resolved,
+    against want[i] = oracle_keys at the round-start state and the results r
+    (res_array): the listed keys are the oracle's top ones, the bound covers
+    the next feasible key, the feasible count matches.  Returns the number of
+    keys listed over all pods."""
+    out = (C.c_uint64 * (2 + K))()
+    listed = 0
+    for i in range(m):
+        assert s.lib.ks_debug_round_record(s.ctx, i, out) == 0, s.lib.ks_last_error(s.ctx)
+        bound, nk = int(out[0]), int(out[1])
+        got = np.array(out[2:2 + nk], dtype=np.uint64)
+        keys, nfeas = want[i]
+        assert int(r["feasible"][i]) == nfeas or r["status"][i] != 0
+        assert nk <= len(keys)
+        assert np.array_equal(got, keys[:nk]), f"pod {i}: listed keys differ from the oracle's top {nk}"
+        if nk < len(keys):
+            assert bound >= int(keys[nk]), f"pod {i}: bound below an unlisted feasible key"
+        listed += nk
+    return listed
+
+
 STATE_DT = np.dtype([("alloc_cpu", "<i8"), ("alloc_mem", "<i8"), ("req_cpu", "<i8"), ("req_mem", "<i8"),
                      ("nz_cpu", "<i8"), ("nz_mem", "<i8"), ("alloc_pods", "<i4"), ("pod_count", "<i4")])
 

@@ -12,22 +12,13 @@ listed node -- dozens to hundreds per pod -- not only the chosen one.
 """
 import ctypes as C
 
-import numpy as np
 import pytest
 
 import pyoracle
-from helpers import res_array, scores_array
+from helpers import assert_round_records, oracle_keys, res_array
 from ksched import Scheduler, synth
 
 pytestmark = pytest.mark.gpu
-
-
-def oracle_keys(o, pod_ptr):
-    sc = scores_array(o.plugin_scores(pod_ptr))
-    feas = np.nonzero(sc[:, 0] == -1)[0]
-    keys = ((sc[feas, -1].astype(np.uint64) + np.uint64(1)) << np.uint64(32)) | (
-        np.uint64(0xFFFFFFFF) - feas.astype(np.uint64))
-    return np.sort(keys)[::-1], len(feas)
 
 
 @pytest.mark.parametrize("kind,seeds,vshards", [(synth.HETERO, (1, 2), 1), (synth.LABELED, (4, 5), 1),
@@ -52,19 +43,7 @@ def test_round_records_match_oracle(kind, seeds, vshards):
     # one round resolved every pod: the parity-0 records are round 0's, swept
     # against the round-start state (a re-sweep would overwrite them)
     assert dbg[0] == 1, f"{dbg[0]} rounds: round 0 stopped early and its records were re-swept"
-    out = (C.c_uint64 * (2 + K))()
-    listed = 0
-    for i in range(m):
-        assert s.lib.ks_debug_round_record(s.ctx, i, out) == 0, s.lib.ks_last_error(s.ctx)
-        bound, nk = int(out[0]), int(out[1])
-        got = np.array(out[2:2 + nk], dtype=np.uint64)
-        keys, nfeas = want[i]
-        assert int(r["feasible"][i]) == nfeas or r["status"][i] != 0
-        assert nk <= len(keys)
-        assert np.array_equal(got, keys[:nk]), f"pod {i}: listed keys differ from the oracle's top {nk}"
-        if nk < len(keys):
-            assert bound >= int(keys[nk]), f"pod {i}: bound below an unlisted feasible key"
-        listed += nk
+    listed = assert_round_records(s, want, r, m, K)
     assert listed >= m * 8, f"only {listed} keys listed over {m} pods"
     s.close()
     o.close()
