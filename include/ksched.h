@@ -341,7 +341,7 @@ typedef struct {
 /* Per-node plugin scores of one pod (parity dump; NodePluginScores analogue). */
 typedef struct {
   int32_t status;        /* -1 feasible, else KS_PLUGIN_* of the first failing filter, -2 empty slot */
-  int32_t least_allocated;      /* NodeResourcesFit (LeastAllocated)     */
+  int32_t least_allocated;      /* NodeResourcesFit, under the strategy in force (ks_set_fit_strategy) */
   int32_t balanced_allocation;  /* NodeResourcesBalancedAllocation       */
   int32_t taint_raw;            /* TaintToleration raw (before normalize) */
   int32_t taint_score;          /* TaintToleration normalized            */
@@ -658,6 +658,36 @@ ks_status ks_debug_runs_started(ks_ctx *ctx, uint64_t *out);
 /* 1 = time sweep / resolve launches with HIP events (every KS_TIMING_EVERY-th
  * round, default 8; sweep_evals counts the timed launches' share), 0 = off. */
 ks_status ks_set_timing(ks_ctx *ctx, int32_t enabled);
+/* NodeResourcesFitArgs.scoringStrategy: LeastAllocated or MostAllocated over
+ * {cpu, memory} with per-resource weights (upstream v1.31.3
+ * noderesources/{least,most}_allocated.go, resource_allocation.go).  Per scored
+ * resource with non-zero Allocatable, requested = the node's NonZeroRequested +
+ * the pod's non-zero request:
+ *   LeastAllocated  requested > capacity ? 0 : (capacity - requested) * 100 / capacity
+ *   MostAllocated   min(requested, capacity) * 100 / capacity
+ * and the node score is sum(score x weight) / sum(weight) over those resources
+ * (int64 truncation; 0 when no weight is left).  Weights are 0..100; 0 means
+ * the resource is not listed; both 0, a weight outside 0..100 or an unknown
+ * type: KS_ERR_INVALID.  The default is {KS_FIT_LEAST_ALLOCATED, 1, 1}.
+ * The call waits for submitted batches; the strategy then applies to every
+ * batch RUN after it (also one prepared before), to ks_plugin_scores
+ * (ks_node_score.least_allocated carries the score under it) and to
+ * ks_debug_round_record.  With several ranks every rank sets the same strategy
+ * (the caller's duty, as for the plugin weights).
+ * On a context with percentage_of_nodes_to_score < 100 any strategy but the
+ * default returns KS_ERR_UNSUPPORTED: the window's only reference is the
+ * oracle's own schedule, which knows the default strategy alone, and nothing
+ * ships here that a parity test does not pin.
+ * RequestedToCapacityRatio and extended resources in the list: not modelled. */
+enum { KS_FIT_LEAST_ALLOCATED = 0, KS_FIT_MOST_ALLOCATED = 1 };
+typedef struct {
+  int32_t type;           /* KS_FIT_*                       */
+  int32_t weight_cpu;     /* resources: {name: cpu, weight}    */
+  int32_t weight_memory;  /* resources: {name: memory, weight} */
+  int32_t _pad;
+} ks_fit_strategy;
+ks_status ks_set_fit_strategy(ks_ctx *ctx, const ks_fit_strategy *s);
+ks_status ks_get_fit_strategy(ks_ctx *ctx, ks_fit_strategy *out);
 
 #ifdef __cplusplus
 }

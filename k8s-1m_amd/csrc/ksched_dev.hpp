@@ -309,4 +309,20 @@ struct Weights {
   int32_t fit, ba, tt, na, il;
 };
 
+// NodeResourcesFit scoring strategy other than {LeastAllocated, cpu 1, memory 1}
+// (ks_set_fit_strategy).  Read only by the kernels' general
+// variants (template parameter GF); the default strategy's instantiations
+// never load it.  The node score is (wc s_cpu + wm s_mem) / d with d the summed
+// weight of the resources whose allocatable is non-zero: floor(n / d) for
+// n <= 20000 is (2 n x rcp) >> 32 with rcp = ceil(2^31 / d), 0 for d == 0
+// (fit_weight_rcp; checked over the whole domain by tools/fit_check.cpp).
+struct FitParams {
+  uint32_t most;                       // 1 MostAllocated, 0 LeastAllocated
+  uint32_t wc, wm;                     // resource weights, 0..100 (0: not listed)
+  uint32_t rcp_cpu, rcp_mem, rcp_both; // d = wc, wm, wc + wm
+};
+__host__ __device__ inline uint32_t fit_weight_rcp(uint32_t d) {
+  return d ? (uint32_t)(((1ull << 31) + d - 1) / d) : 0u;
+}
+
 }  // namespace ks

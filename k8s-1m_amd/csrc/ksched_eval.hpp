@@ -235,6 +235,48 @@ __device__ __forceinline__ int32_t score_la(const PodDev &p, const NodeRegs &r) 
          r.lashift;
 }
 
+// One resource's score under the general strategy.  LeastAllocated is
+// least_requested.  mostRequestedScore(requested, capacity) =
+// min(requested, capacity) * 100 / capacity: requested * 100 = cap100 - x with
+// x = lf100 - nz100 as above (every term an integer below 2^53, so exact), the
+// clamp is the min with cap100, and the same one-FMA floor applies: the
+// numerator is a multiple of 100 in [0, cap100].  inv == 0 -> 0.  DESIGN.md §4;
+// checked by tools/fit_check.cpp.
+__device__ __forceinline__ uint32_t fit_resource(bool most, double lf100, double pod_nz100, double cap, double inv) {
+  double x = lf100 - pod_nz100;
+  const double cap100 = cap * 100.0;  // exact (cap < 2^44)
+  if (most) x = fmin(cap100 - x, cap100);
+  const double q = __builtin_fma(x, inv, LA_EPS);
+  uint32_t r;
+  asm("v_cvt_u32_f64 %0, %1" : "=v"(r) : "v"(q));  // a negative q (LeastAllocated, requested > capacity) gives 0
+  return r;
+}
+
+// NodeResourcesFit's score.  GF == false: {LeastAllocated, 1, 1}, the code
+// every default context runs.  GF == true: the context's strategy f
+// (resource_allocation.go#score): sum of weight x resource score over the
+// resources with non-zero allocatable, divided by their summed weight by a
+// reciprocal multiply (FitParams); a zero weight sum gives n == 0 -> 0.
+// (nz100_cpu / nz100_mem: the pod's non-zero requests x 100, PodDev's fields)
+__device__ __forceinline__ int32_t score_fit_general(double nz100_cpu, double nz100_mem, const NodeRegs &r,
+                                                     const FitParams &f) {
+  const uint32_t sc = fit_resource(f.most, r.lf100_cpu, nz100_cpu, r.acpu_d, r.inv_cpu);
+  const uint32_t sm = fit_resource(f.most, r.lf100_mem, nz100_mem, r.amem_d, r.inv_mem);
+  const uint32_t n = wmad(f.wc, sc, wmul(f.wm, sm));  // <= 20000
+  // the three reciprocals as scalar registers: a select between the loads
+  // themselves becomes one load through a per-lane address
+  const uint32_t rb = __builtin_amdgcn_readfirstlane(f.rcp_both), rc = __builtin_amdgcn_readfirstlane(f.rcp_cpu),
+                 rm = __builtin_amdgcn_readfirstlane(f.rcp_mem);
+  const bool hc = r.inv_cpu != 0.0, hm = r.inv_mem != 0.0;
+  const uint32_t rcp = hc ? (hm ? rb : rc) : rm;
+  return (int32_t)__umulhi(n << 1, rcp);
+}
+template <bool GF>
+__device__ __forceinline__ int32_t score_fit(const PodDev &p, const NodeRegs &r, const FitParams &f) {
+  if constexpr (!GF) return score_la(p, r);
+  else return score_fit_general(p.nz100_cpu, p.nz100_mem, r, f);
+}
+
 // RN(a / b) from y = RN(1 / b): q0 = RN(a y) is within one ulp of a/b, the
 // remainder a - b q0 is exact by FMA, and one correction q0 + r y rounds to the
 // IEEE quotient (Markstein).  Checked against true division over the operand
@@ -274,11 +316,11 @@ __device__ __forceinline__ int64_t normalize(int64_t raw, int64_t mx, bool rever
 
 // Plugin scores are in [0, 100] and ks_open caps the weights at 10000, so the
 // weighted sum fits 23 bits: 24-bit multiplies, 32-bit adds.
-template <bool EXT>
+template <bool EXT, bool GF>
 __device__ __forceinline__ int32_t total_score(const PodDev &p, const uint64_t *clauses, const NodeRegs &r,
-                                               const NodeExt &e, const Weights &w, int64_t tt_max,
-                                               int64_t na_max) {
-  int32_t t = (int32_t)wmul((uint32_t)w.fit, (uint32_t)score_la(p, r)) +
+                                               const NodeExt &e, const Weights &w, const FitParams &fs,
+                                               int64_t tt_max, int64_t na_max) {
+  int32_t t = (int32_t)wmul((uint32_t)w.fit, (uint32_t)score_fit<GF>(p, r, fs)) +
               (int32_t)wmul((uint32_t)w.ba, (uint32_t)score_ba(p, r));
   int32_t tt = 100;
   if (EXT && (p.flags & PF_TT)) tt = (int32_t)normalize(taint_raw(p, e), tt_max, true);

@@ -398,6 +398,12 @@ struct ks_ctx {
   // ks_debug_stall: the next round holds back flag stall_flag's signal by stall_us
   int32_t stall_flag = -1;
   uint32_t stall_us = 0;
+  // NodeResourcesFit scoring strategy (ks_set_fit_strategy), read when a
+  // round / chain / dump is enqueued; fit_general: not {LeastAllocated, 1, 1},
+  // the launchers take the kernels' general variants with fit_params
+  ks_fit_strategy fit{KS_FIT_LEAST_ALLOCATED, 1, 1, 0};
+  FitParams fit_params{0, 1, 1, fit_weight_rcp(1), fit_weight_rcp(1), fit_weight_rcp(2)};
+  uint32_t fit_general = 0;
   // Execution options from ks_config (ks_open), per context, so one process
   // can open contexts with different settings (tests do).
   bool early_fix = true;
@@ -2921,6 +2927,8 @@ ks_status enqueue_round(ks_ctx *c, ks_batch *b, uint32_t k, uint32_t end) {
   a.slot_pos = c->d_slot_pos;
   a.w = Weights{c->cfg.weight_fit, c->cfg.weight_balanced, c->cfg.weight_taint, c->cfg.weight_affinity,
                 c->cfg.weight_image};
+  a.fs = c->fit_params;
+  a.fit_general = c->fit_general;
   if ((size_t)nloc * c->P * bmax * sizeof(BlockRec) > c->brec_bytes)
     return c->fail(KS_ERR_INVALID, "block record buffer too small");
 
@@ -4536,6 +4544,8 @@ SpreadArgs spread_args(ks_ctx *c) {
   sa.counters = c->d_counters;
   sa.w = Weights{c->cfg.weight_fit, c->cfg.weight_balanced, c->cfg.weight_taint, c->cfg.weight_affinity,
                  c->cfg.weight_image};
+  sa.fs = c->fit_params;
+  sa.fit_general = c->fit_general;
   sa.w_pts = c->cfg.weight_topology_spread;
   sa.w_ipa = c->cfg.weight_inter_pod_affinity;
   sa.evaluated = c->n_present;
@@ -4605,6 +4615,8 @@ ks_status ks_plugin_scores(ks_ctx *c, const ks_pod *pod, ks_node_score *out) {
   a.nslots = c->cap;
   a.w = Weights{c->cfg.weight_fit, c->cfg.weight_balanced, c->cfg.weight_taint, c->cfg.weight_affinity,
                 c->cfg.weight_image};
+  a.fs = c->fit_params;
+  a.fit_general = c->fit_general;
   a.slot_pos = c->d_slot_pos;
   std::vector<int32_t> raw((size_t)c->cap * 10);
   const size_t bytes = sizeof(PodDev) + cl.w.size() * 8 + 8 + raw.size() * 4 + 2048;
@@ -4842,6 +4854,33 @@ ks_status ks_debug_sweep_geometry(ks_ctx *c, int32_t ext, uint64_t out[8]) {
   if (!c || !out) return KS_ERR_INVALID;
   if (ks_status dst_ = drain_async(c)) return dst_;
   std::memcpy(out, c->sweep_geom[ext ? 1 : 0], sizeof c->sweep_geom[0]);
+  return KS_OK;
+}
+
+ks_status ks_set_fit_strategy(ks_ctx *c, const ks_fit_strategy *s) {
+  if (!c || !s) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  if (s->type != KS_FIT_LEAST_ALLOCATED && s->type != KS_FIT_MOST_ALLOCATED) return KS_ERR_INVALID;
+  if (s->weight_cpu < 0 || s->weight_cpu > 100 || s->weight_memory < 0 || s->weight_memory > 100 ||
+      (s->weight_cpu == 0 && s->weight_memory == 0))
+    return KS_ERR_INVALID;
+  const bool general = !(s->type == KS_FIT_LEAST_ALLOCATED && s->weight_cpu == 1 && s->weight_memory == 1);
+  // the window's only reference is the oracle's own schedule, which knows the default strategy alone
+  if (general && c->pct != 100) return KS_ERR_UNSUPPORTED;
+  std::lock_guard<std::mutex> g(c->mu);
+  c->fit = ks_fit_strategy{s->type, s->weight_cpu, s->weight_memory, 0};
+  const uint32_t wc = (uint32_t)s->weight_cpu, wm = (uint32_t)s->weight_memory;
+  c->fit_params = FitParams{s->type == KS_FIT_MOST_ALLOCATED ? 1u : 0u, wc, wm, fit_weight_rcp(wc), fit_weight_rcp(wm),
+                            fit_weight_rcp(wc + wm)};
+  c->fit_general = general ? 1u : 0u;
+  return KS_OK;
+}
+
+ks_status ks_get_fit_strategy(ks_ctx *c, ks_fit_strategy *out) {
+  if (!c || !out) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  std::lock_guard<std::mutex> g(c->mu);
+  *out = c->fit;
   return KS_OK;
 }
 

@@ -176,11 +176,15 @@ __device__ __forceinline__ uint32_t normalize_inv(uint32_t raw, double inv) {
 // grid: x = block within shard, y = pod group, z = local shard.
 constexpr uint32_t KEY32_POS_BITS = 9, KEY32_POS_MASK = (1u << KEY32_POS_BITS) - 1;
 
-template <int NPL, bool EXT, int LWU = LW>
+// GF: the NodeResourcesFit score under the context's strategy (score_fit,
+// a.fs) instead of {LeastAllocated, 1, 1}: instances of
+// their own, so the default strategy's kernels are the code they were.
+template <int NPL, bool EXT, int LWU = LW, bool GF = false>
 // EXT with 2 nodes per lane: 5 waves per SIMD (91 VGPRs) runs the C4 sweep
 // 5 % faster than 4 (103 VGPRs); 6 waves spill 72 B; the resource-only
-// kernel at 5 waves spills 20 B and measured 9 % slower (kept at 4)
-__global__ __launch_bounds__(SWEEP_THREADS) __attribute__((amdgpu_waves_per_eu(EXT && NPL == 2 ? 5 : 1)))
+// kernel at 5 waves spills 20 B and measured 9 % slower (kept at 4).  The
+// general variants keep 4 waves (at 5 the scorer's registers spill up to 60 B)
+__global__ __launch_bounds__(SWEEP_THREADS) __attribute__((amdgpu_waves_per_eu(EXT && NPL == 2 && !GF ? 5 : 1)))
 void sweep_kernel(RoundArgs a) {
   static_assert(NPL * WAVE <= (1 << KEY32_POS_BITS), "wave-local key position field");
   constexpr int NW = SWEEP_THREADS / WAVE;
@@ -278,7 +282,7 @@ void sweep_kernel(RoundArgs a) {
                             (zm | __builtin_amdgcn_ballot_w64(!(sm > nr[j].amem_d)));
         // key = (w_fit LA + w_ba BA) << 9 + kc[j]: two 24-bit multiply-adds
         // with the weights pre-shifted (10000 << 9 < 2^24; the key < 2^31)
-        const uint32_t key = sel_mask(fm, wmad_s(wf9, (uint32_t)score_la(p, nr[j]),
+        const uint32_t key = sel_mask(fm, wmad_s(wf9, (uint32_t)score_fit<GF>(p, nr[j], a.fs),
                                                  wmad_s(wb9, (uint32_t)score_ba_sum(sc, sm, nr[j]), kc[j])));
         b2 = max(b2, min(b1, key));
         b1 = max(b1, key);
@@ -353,7 +357,7 @@ void sweep_kernel(RoundArgs a) {
           acc = wmad_s(wn9, nas, acc);
         }
         acc = wmad_s(wb9, (uint32_t)score_ba_sum(sc, sm, nr[j]), acc);
-        acc = wmad_s(wf9, (uint32_t)score_la(p, nr[j]), acc);
+        acc = wmad_s(wf9, (uint32_t)score_fit<GF>(p, nr[j], a.fs), acc);
         const uint32_t key = sel_mask(fb, acc);
         b2 = max(b2, min(b1, key));
         b1 = max(b1, key);
@@ -787,7 +791,7 @@ __device__ __forceinline__ uint32_t count_greater(const uint64_t *v, uint32_t n,
 }
 
 
-template <bool EXT, int PATCH_THREADS>
+template <bool EXT, int PATCH_THREADS, bool GF = false>
 __global__ __launch_bounds__(PATCH_THREADS) void patch_kernel(RoundArgs a) {
   static_assert(PATCH_THREADS >= MAX_P, "one thread per carried node");
   constexpr int NW = PATCH_THREADS / WAVE;
@@ -837,7 +841,7 @@ __global__ __launch_bounds__(PATCH_THREADS) void patch_kernel(RoundArgs a) {
     r0.bits = (r1.bits & ~2u) | ((int64_t)cr.np0 + 1 <= (int64_t)cr.apods ? 2u : 0u);
     const int st0 = filter<EXT>(p, a.clauses, r0, ce);
     const int st1 = filter<EXT>(p, a.clauses, r1, ce);
-    if (st1 == ST_FEASIBLE) k1 = pack_key(total_score<EXT>(p, a.clauses, r1, ce, a.w, tt_max, na_max), cr.slot);
+    if (st1 == ST_FEASIBLE) k1 = pack_key(total_score<EXT, GF>(p, a.clauses, r1, ce, a.w, a.fs, tt_max, na_max), cr.slot);
     if (st0 != st1) status_delta<EXT>(p, a.clauses, st0, st1, ce, cr.slot, tt_max, na_max, d);
     uint32_t h = rhash(cr.slot);
     while (atomicCAS(&s_hkey[h], 0u, cr.slot + 1) != 0u) h = (h + 1) & (PHASH - 1);
@@ -1155,7 +1159,7 @@ __global__ void dump_scores_kernel(DumpArgs a) {
   o[0] = st;
   if (st != ST_FEASIBLE) return;
   const int64_t tt_max = a.norm_max[0], na_max = a.norm_max[1];
-  o[1] = (int32_t)score_la(p, r);
+  o[1] = a.fit_general ? score_fit<true>(p, r, a.fs) : score_fit<false>(p, r, a.fs);
   o[2] = (int32_t)score_ba(p, r);
   const int64_t tr = (p.flags & PF_TT) ? taint_raw(p, e) : 0;
   o[3] = (int32_t)tr;
@@ -1164,7 +1168,8 @@ __global__ void dump_scores_kernel(DumpArgs a) {
   o[5] = (int32_t)nr;
   o[6] = (p.flags & PF_HAS_PREF) ? (int32_t)normalize(nr, (p.flags & PF_NA) ? na_max : 0, false) : 0;
   o[7] = 0;
-  const int64_t tot = total_score<true>(p, a.clauses, r, e, a.w, tt_max, na_max);
+  const int64_t tot = a.fit_general ? total_score<true, true>(p, a.clauses, r, e, a.w, a.fs, tt_max, na_max)
+                                    : total_score<true, false>(p, a.clauses, r, e, a.w, a.fs, tt_max, na_max);
   o[8] = (int32_t)(tot & 0xFFFFFFFF);
   o[9] = (int32_t)(tot >> 32);
 }
@@ -1185,6 +1190,28 @@ hipError_t launch_norm_check(const RoundArgs &a, hipStream_t st) {
 hipError_t launch_sweep(const RoundArgs &a, bool ext, uint32_t nblocks, uint32_t ngroups, uint32_t nshards,
                         hipStream_t st) {
   dim3 g(nblocks, ngroups, nshards);
+  if (a.fit_general) {
+    if (ext) {
+      // label words in use (dictionary size): 1, 2 or 4 words per node are read
+      const uint32_t lwu = sweep_label_words(a.npl, a.t.lw);
+      if (a.npl == 2) {
+        if (lwu == 1) sweep_kernel<2, true, 1, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+        else if (lwu == 2) sweep_kernel<2, true, 2, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+        else sweep_kernel<2, true, 4, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+      } else if (a.npl == 4) {
+        if (lwu == 1) sweep_kernel<4, true, 1, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+        else if (lwu == 2) sweep_kernel<4, true, 2, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+        else sweep_kernel<4, true, 4, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+      } else {
+        sweep_kernel<8, true, 4, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+      }
+    } else {
+      if (a.npl == 2) sweep_kernel<2, false, LW, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+      else if (a.npl == 4) sweep_kernel<4, false, LW, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+      else sweep_kernel<8, false, LW, true><<<g, SWEEP_THREADS, 0, st>>>(a);
+    }
+    return hipGetLastError();
+  }
   if (ext) {
     // label words in use (dictionary size): 1, 2 or 4 words per node are read
     const uint32_t lwu = sweep_label_words(a.npl, a.t.lw);
@@ -1239,6 +1266,16 @@ hipError_t launch_writeback(const NodeTable &t, const CarryRec *carry, const uin
 }
 
 hipError_t launch_patch(const RoundArgs &a, bool ext, hipStream_t st) {
+  if (a.fit_general) {
+    if (a.K <= (uint32_t)MAX_P) {
+      if (ext) patch_kernel<true, MAX_P, true><<<a.P, MAX_P, 0, st>>>(a);
+      else patch_kernel<false, MAX_P, true><<<a.P, MAX_P, 0, st>>>(a);
+    } else {
+      if (ext) patch_kernel<true, MAX_K, true><<<a.P, MAX_K, 0, st>>>(a);
+      else patch_kernel<false, MAX_K, true><<<a.P, MAX_K, 0, st>>>(a);
+    }
+    return hipGetLastError();
+  }
   if (a.K <= (uint32_t)MAX_P) {
     if (ext) patch_kernel<true, MAX_P><<<a.P, MAX_P, 0, st>>>(a);
     else patch_kernel<false, MAX_P><<<a.P, MAX_P, 0, st>>>(a);

@@ -94,6 +94,8 @@ struct RoundArgs {
                               // [4] FIX re-swept pods, [7] identical pods not swept (their class's
                               // representative was; [2] counts representatives), [CTR_PAR_*]
   Weights w;
+  FitParams fs;               // NodeResourcesFit strategy of the general kernel variants ...
+  uint32_t fit_general;       // ... which the launchers choose when set (not {LeastAllocated, 1, 1})
 };
 
 struct DumpArgs {
@@ -105,6 +107,8 @@ struct DumpArgs {
   uint32_t *norm_max;         // [2], zeroed
   int32_t *out;               // [nslots][10]
   Weights w;
+  FitParams fs;
+  uint32_t fit_general;
 };
 
 // PodTopologySpread path (ksched_spread.hip): one pod per launch chain.
@@ -142,6 +146,8 @@ struct SpreadArgs {
   uint32_t no_commit;         // dump / reset: no result, no AssumePod
   uint64_t *counters;
   Weights w;
+  FitParams fs;               // as RoundArgs::fs / fit_general
+  uint32_t fit_general;
   int32_t w_pts, w_ipa;
   uint32_t evaluated;         // present nodes
   // percentageOfNodesToScore < 100 (ksched_spread.hip spread_window_kernel):

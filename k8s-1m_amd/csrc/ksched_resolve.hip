@@ -185,8 +185,9 @@ __device__ __forceinline__ XS px_static(const PX &x, const uint64_t *clauses, co
 // packed key of the pod on the row's live state (0: infeasible): key_q on
 // rnode_regs, with the resource-free score part ss (w_tt x 100 for a
 // resource-only pod)
+template <bool GF>
 __device__ __forceinline__ uint64_t pq_key_ss(const PQ &q, const CandRow &r, uint32_t slot, const Weights &w,
-                                              int32_t ss) {
+                                              const FitParams &fs, int32_t ss) {
   if (!pq_fit(q, r, r.rc, r.rm, r.np)) return 0;
   NodeRegs g;
   g.free_cpu = r.acpu - r.rc;
@@ -203,14 +204,20 @@ __device__ __forceinline__ uint64_t pq_key_ss(const PQ &q, const CandRow &r, uin
   g.bamul = (ac && am) ? 0.5 : 0.0;
   g.lashift = (ac && am) ? 1u : 0u;
   g.slot = slot;
-  const int32_t la = (least_requested(g.lf100_cpu, q.zc, g.inv_cpu) + least_requested(g.lf100_mem, q.zm, g.inv_mem)) >>
-                     g.lashift;
+  int32_t la;
+  if constexpr (GF) {
+    la = score_fit_general(q.zc, q.zm, g, fs);
+  } else {
+    la = (least_requested(g.lf100_cpu, q.zc, g.inv_cpu) + least_requested(g.lf100_mem, q.zm, g.inv_mem)) >> g.lashift;
+  }
   const int32_t ba = score_ba_sum(g.rcpu + q.rc, g.rmem + q.rm, g);
   const int32_t t = (int32_t)wmul((uint32_t)w.fit, (uint32_t)la) + (int32_t)wmul((uint32_t)w.ba, (uint32_t)ba) + ss;
   return pack_key(t, slot);
 }
-__device__ __forceinline__ uint64_t pq_key(const PQ &q, const CandRow &r, uint32_t slot, const Weights &w) {
-  return pq_key_ss(q, r, slot, w, w.tt * 100);
+template <bool GF>
+__device__ __forceinline__ uint64_t pq_key(const PQ &q, const CandRow &r, uint32_t slot, const Weights &w,
+                                           const FitParams &fs) {
+  return pq_key_ss<GF>(q, r, slot, w, fs, w.tt * 100);
 }
 
 // One (pod, node) pair of a round: the key on the node's live row and the
@@ -223,10 +230,10 @@ struct PairEval {
   int32_t lost;
   uint32_t at_lost;
 };
-template <bool EXT>
+template <bool EXT, bool GF>
 __device__ __forceinline__ PairEval pair_eval(const PQ &q, const PX *px, const uint64_t *clauses, const CandRow &r,
                                               const CandExt *cx, uint32_t slot, double rc0, double rm0, int32_t np0,
-                                              const Weights &w) {
+                                              const Weights &w, const FitParams &fs) {
   PairEval v;
   int32_t ss = w.tt * 100;
   uint32_t at = 0;
@@ -241,7 +248,7 @@ __device__ __forceinline__ PairEval pair_eval(const PQ &q, const PX *px, const u
     ss = xs.ss;
     at = xs.at;
   }
-  v.key = pq_key_ss(q, r, slot, w, ss);
+  v.key = pq_key_ss<GF>(q, r, slot, w, fs, ss);
   v.lost = (pq_fit(q, r, rc0, rm0, np0) ? 1 : 0) - (v.key != 0 ? 1 : 0);
   v.at_lost = v.lost ? at : 0u;
   return v;
@@ -368,7 +375,7 @@ __device__ __forceinline__ SerialLds<EXT, LIST_SPAN> *ser_lds() {
 // Returns true when it resolved the round (or found it wasted); false when
 // the serial commit must take it (RESOLVE_SERIAL, a serial stretch of
 // RESOLVE_AUTO, or a hand-over from this round)
-template <bool EXT>
+template <bool EXT, bool GF>
 __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
   constexpr int NC = EXT ? PNC_EXT : PNC;      // candidates gathered per chunk pod
   constexpr int NR = EXT ? PNR_EXT : PNR;      // ... whose rows are prefetched
@@ -604,7 +611,12 @@ __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
     if (tid < n && s_rep[tid] != s_rep[0]) s_ic[1] = 1;  // more than one pod class
     if (tid == 0 && (n < 2 || a.rep == nullptr || h0.feasible == 0 || (s_fl[0] & PF_PREF_ERR) || h0.nkeys == 0))
       s_ic[1] = 1;
-    const bool check_all = q0.rc != 0.0 || q0.rm != 0.0;  // requests: BalancedAllocation moves
+    // requests: BalancedAllocation moves.  Under MostAllocated the non-zero
+    // defaults of a request-less pod raise the key as the node fills (the
+    // "only falls" above is LeastAllocated's): every listed node is followed
+    // to its end, and the first rise sends the round to the passes; the
+    // closed form keeps the rounds whose keys stay flat
+    const bool check_all = q0.rc != 0.0 || q0.rm != 0.0 || (GF && a.fs.most);
     __syncthreads();
     if (s_ic[1] == 0) {
       const uint32_t nk = min(h0.nkeys, (uint32_t)MAX_K);
@@ -615,7 +627,7 @@ __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
         const uint32_t slot = key_slot(keys0[tid]);
         uint64_t prev = ~0ull;
         for (uint32_t k = 0; k < n; ++k) {
-          const uint64_t key = pq_key(q0, r, slot, a.w);
+          const uint64_t key = pq_key<GF>(q0, r, slot, a.w, a.fs);
           if (key > prev) {  // not non-increasing: the general passes
             s_ic[1] = 1;
             break;
@@ -763,8 +775,8 @@ __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
         const uint32_t mn = s_ctl[5];
         for (uint32_t m = lane; m < mn; m += WAVE) {
           const RNode &x = s_m[m];
-          best = max64(best, pair_eval<EXT>(q, &s_px[EXT ? jt[t] : 0], a.clauses, x.row, &s_mx[EXT ? m : 0], x.slot,
-                                            x.rc0, x.rm0, x.np0, a.w).key);
+          best = max64(best, pair_eval<EXT, GF>(q, &s_px[EXT ? jt[t] : 0], a.clauses, x.row, &s_mx[EXT ? m : 0], x.slot,
+                                            x.rc0, x.rm0, x.np0, a.w, a.fs).key);
         }
         rkt[t] = wave_max_u64_dpp(best);
         if (lane == 0) {
@@ -989,8 +1001,8 @@ __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
         const int32_t np0 = r.np;
         for (uint32_t k = ic; k != PNONE && k < jc; k = s_pnx[k]) pq_add(r, s_q[f + k]);
         const PQ q = s_q[f + jc];
-        const PairEval v = pair_eval<EXT>(q, &s_px[EXT ? f + jc : 0], a.clauses, r, &s_prowx[EXT ? ic : 0],
-                                          s_prow[ic].slot, rc0, rm0, np0, a.w);
+        const PairEval v = pair_eval<EXT, GF>(q, &s_px[EXT ? f + jc : 0], a.clauses, r, &s_prowx[EXT ? ic : 0],
+                                          s_prow[ic].slot, rc0, rm0, np0, a.w, a.fs);
         if (v.key) atomicMax((unsigned long long *)&s_ik[jc], (unsigned long long)v.key);
         if (v.lost) atomicAdd(&s_idl[jc], v.lost);
         if (EXT && v.at_lost) atomicAdd(&s_idn[EXT ? jc : 0], (v.at_lost & 1u) | (v.at_lost >> 1) << 16);
@@ -1176,8 +1188,8 @@ __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
           const uint32_t d = t / npend, jj = nf + t % npend;
           const RNode &x = s_m[s_cdm[d]];
           const PQ q = s_q[jj];
-          const PairEval v = pair_eval<EXT>(q, &s_px[EXT ? jj : 0], a.clauses, x.row, &s_mx[EXT ? s_cdm[d] : 0],
-                                            x.slot, s_cdp[d][0], s_cdp[d][1], s_cdn[d], a.w);
+          const PairEval v = pair_eval<EXT, GF>(q, &s_px[EXT ? jj : 0], a.clauses, x.row, &s_mx[EXT ? s_cdm[d] : 0],
+                                            x.slot, s_cdp[d][0], s_cdp[d][1], s_cdn[d], a.w, a.fs);
           const uint64_t key = v.key;
           if (v.lost) atomicAdd(&s_dl[jj], v.lost);
           if (EXT && v.at_lost) atomicAdd(&s_dn[EXT ? jj : 0], (v.at_lost & 1u) | (v.at_lost >> 1) << 16);
@@ -1324,16 +1336,28 @@ __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
 // commit's (RESOLVE_SERIAL, a serial stretch, a hand-over).  The two share
 // one LDS allocation (a union: each is within the CU's 160 KB on its own);
 // the serial commit reads nothing the parallel one wrote to LDS.
-template <bool EXT, int LIST_SPAN>
+// GF: under the general NodeResourcesFit strategy (RoundArgs::fs)
+template <bool EXT, int LIST_SPAN, bool GF = false>
 __global__ __launch_bounds__(PR_THREADS) void resolve_kernel(RoundArgs a) {
   static_assert(PR_THREADS == RESOLVE_THREADS, "both commits run on one 1024-thread workgroup");
-  if (resolve_parallel<EXT>(a)) return;
+  if (resolve_parallel<EXT, GF>(a)) return;
   __syncthreads();  // the parallel commit's last LDS reads, its hand-over writes (rmode)
-  resolve_serial<EXT, LIST_SPAN>(a);
+  resolve_serial<EXT, LIST_SPAN, GF>(a);
 }
 
 hipError_t launch_resolve(const RoundArgs &a, bool ext, hipStream_t st) {
-  if (a.K <= (uint32_t)(RES_LIST_WAVES * LIST_SPAN_1)) {
+  const bool one = a.K <= (uint32_t)(RES_LIST_WAVES * LIST_SPAN_1);
+  if (a.fit_general) {
+    if (one) {
+      if (ext) resolve_kernel<true, LIST_SPAN_1, true><<<1, PR_THREADS, 0, st>>>(a);
+      else resolve_kernel<false, LIST_SPAN_1, true><<<1, PR_THREADS, 0, st>>>(a);
+    } else {
+      if (ext) resolve_kernel<true, LIST_SPAN_2, true><<<1, PR_THREADS, 0, st>>>(a);
+      else resolve_kernel<false, LIST_SPAN_2, true><<<1, PR_THREADS, 0, st>>>(a);
+    }
+    return hipGetLastError();
+  }
+  if (one) {
     if (ext) resolve_kernel<true, LIST_SPAN_1><<<1, PR_THREADS, 0, st>>>(a);
     else resolve_kernel<false, LIST_SPAN_1><<<1, PR_THREADS, 0, st>>>(a);
   } else {

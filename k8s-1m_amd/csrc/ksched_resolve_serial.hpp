@@ -122,8 +122,9 @@ __device__ __forceinline__ PodQ pod_q(const PodDev &p, const Weights &w) {
 __device__ __forceinline__ bool fit_q(const PodQ &q, const NodeRegs &g) {
   return (g.bits & 2u) && !(q.rq_c > g.free_cpu) && !(q.rq_m > g.free_mem);
 }
-__device__ __forceinline__ uint64_t key_q(const PodDev &p, const PodQ &q, const NodeRegs &g) {
-  const int32_t t = wmul((uint32_t)q.wf, (uint32_t)score_la(p, g)) +
+template <bool GF>
+__device__ __forceinline__ uint64_t key_q(const PodDev &p, const PodQ &q, const NodeRegs &g, const FitParams &fs) {
+  const int32_t t = wmul((uint32_t)q.wf, (uint32_t)score_fit<GF>(p, g, fs)) +
                     wmul((uint32_t)q.wb, (uint32_t)score_ba(p, g)) + q.cplus;
   return pack_key(t, g.slot);
 }
@@ -176,7 +177,7 @@ struct SerialLds {
 template <bool EXT, int LIST_SPAN>
 __device__ __forceinline__ SerialLds<EXT, LIST_SPAN> *ser_lds();
 
-template <bool EXT, int LIST_SPAN>
+template <bool EXT, int LIST_SPAN, bool GF>
 __device__ __forceinline__ void resolve_serial(const RoundArgs &a) {
   constexpr bool TWO = LIST_SPAN == 2 * WAVE;
 #define s_pod (ser_lds<EXT, LIST_SPAN>()->s_pod)
@@ -573,7 +574,7 @@ __device__ __forceinline__ void resolve_serial(const RoundArgs &a) {
           const NodeRegs g0 = rnode_regs(pre, pre.row.rc, pre.row.rm, pre.row.np);
           const NodeRegs g1 = rnode_regs(post, post.row.rc, post.row.rm, post.row.np);
           const bool f0 = fit_q(q1, g0), f1 = fit_q(q1, g1);
-          const uint64_t key = f1 ? key_q(p1, q1, g1) : 0ull;
+          const uint64_t key = f1 ? key_q<GF>(p1, q1, g1, a.fs) : 0ull;
           if (on && cl < (uint32_t)NCAND && r + 1 < nround) {
             s_ekey[buf][cl] = key;
             // a commit only adds: feasible -> Fit failure is the only change
@@ -597,7 +598,7 @@ __device__ __forceinline__ void resolve_serial(const RoundArgs &a) {
             const int st0 = filter<EXT>(p1, a.clauses, g0, e);
             const int st1 = filter<EXT>(p1, a.clauses, g1, e);
             uint64_t key = 0;
-            if (st1 == ST_FEASIBLE) key = pack_key(total_score<EXT>(p1, a.clauses, g1, e, a.w, tt_max, na_max), post.slot);
+            if (st1 == ST_FEASIBLE) key = pack_key(total_score<EXT, GF>(p1, a.clauses, g1, e, a.w, a.fs, tt_max, na_max), post.slot);
             int32_t d[NFILT + 3] = {0, 0, 0, 0, 0, 0, 0, 0};
             if (st0 != st1) status_delta<EXT>(p1, a.clauses, st0, st1, e, post.slot, tt_max, na_max, d);
             s_ekey[buf][cl] = key;
@@ -649,7 +650,7 @@ __device__ __forceinline__ void resolve_serial(const RoundArgs &a) {
           const NodeRegs g = rnode_regs(own, own.row.rc, own.row.rm, own.row.np);
           const NodeRegs g0 = rnode_regs(own, own.rc0, own.rm0, own.np0);
           const bool f0 = fit_q(q1, g0), f = fit_q(q1, g);
-          key = (mine && f) ? key_q(p1, q1, g) : 0ull;
+          key = (mine && f) ? key_q<GF>(p1, q1, g, a.fs) : 0ull;
           dany = mine && f0 && !f;
           // a commit only adds: Fit failures are the only status change
           const int32_t nlost = (int32_t)__popcll(__ballot(dany));
@@ -672,7 +673,7 @@ __device__ __forceinline__ void resolve_serial(const RoundArgs &a) {
           if (mine) {  // p1 above is read by every lane (lds_uniform)
             const int st0 = filter<EXT>(p1, a.clauses, g0, e);
             const int st = filter<EXT>(p1, a.clauses, g, e);
-            if (st == ST_FEASIBLE) key = pack_key(total_score<EXT>(p1, a.clauses, g, e, a.w, tt_max, na_max), own.slot);
+            if (st == ST_FEASIBLE) key = pack_key(total_score<EXT, GF>(p1, a.clauses, g, e, a.w, a.fs, tt_max, na_max), own.slot);
             if (st0 != st) {
               dany = true;
               status_delta<EXT>(p1, a.clauses, st0, st, e, own.slot, tt_max, na_max, d);

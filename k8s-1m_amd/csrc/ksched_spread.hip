@@ -529,7 +529,8 @@ constexpr int RF = NFILT + 2, R_FEAS = RF, R_IGN = RF + 1, R_TT = RF + 2, R_NA =
 // them keeps their prefetched values out of the registers of spread pods.
 // PROBE: the percentageOfNodesToScore probe pass (win_mode 1) -- the filter
 // chain only; as a template parameter the score work compiles away there
-template <bool AFF, bool PROBE = false>
+// GF: NodeResourcesFit scored under the context's strategy (a.fs, score_fit)
+template <bool AFF, bool PROBE = false, bool GF = false>
 __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a) {
   __shared__ uint32_t s_seen[SP_LDS / 32];
   __shared__ uint32_t s_h[SP_LDS];
@@ -703,7 +704,7 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
       const uint32_t nr = (p.flags & PF_NA) ? (uint32_t)preferred_raw(p, a.clauses, e, slot) : 0u;
       tt_max = max(tt_max, tr);
       na_max = max(na_max, nr);
-      a.part[pos] = pack_part((uint32_t)a.w.fit * (uint32_t)score_la(p, r) + (uint32_t)a.w.ba * (uint32_t)score_ba(p, r) +
+      a.part[pos] = pack_part((uint32_t)a.w.fit * (uint32_t)score_fit<GF>(p, r, a.fs) + (uint32_t)a.w.ba * (uint32_t)score_ba(p, r) +
                                   (uint32_t)a.w.il * (uint32_t)image_score(s_solo, e),
                               tr, nr);
       if (ipa_score) {
@@ -1095,7 +1096,7 @@ __global__ __launch_bounds__(SP_THREADS) void spread_select_kernel(SpreadArgs a)
       load_ext(a.t, pos, true, e);
       int32_t *o = a.dump + (size_t)slot * SPREAD_DUMP_WORDS;
       o[0] = ST_FEASIBLE;
-      o[1] = score_la(p, r);
+      o[1] = a.fit_general ? score_fit<true>(p, r, a.fs) : score_fit<false>(p, r, a.fs);
       o[2] = score_ba(p, r);
       const int64_t tr = (p.flags & PF_TT) ? taint_raw(p, e) : 0;
       o[3] = (int32_t)tr;
@@ -1320,6 +1321,7 @@ __device__ __forceinline__ uint32_t run_static(const PodDev &p, const Weights &w
 }
 
 // Sort key of every position (~0: not feasible) after the run's filter pass.
+template <bool GF>
 __global__ __launch_bounds__(SP_THREADS) void replica_keys_kernel(SpreadArgs a, ReplicaArgs r) {
   __shared__ SpreadDev s_sd[MAX_SPREAD];
   __shared__ uint32_t s_max[2];
@@ -1351,7 +1353,7 @@ __global__ __launch_bounds__(SP_THREADS) void replica_keys_kernel(SpreadArgs a, 
     if (skew) {
       NodeRegs g;
       load_core(a.t, pos, slot, true, g);
-      a.part[pos] = pack_part((uint32_t)a.w.fit * (uint32_t)score_la(p, g) + (uint32_t)a.w.ba * (uint32_t)score_ba(p, g),
+      a.part[pos] = pack_part((uint32_t)a.w.fit * (uint32_t)score_fit<GF>(p, g, a.fs) + (uint32_t)a.w.ba * (uint32_t)score_ba(p, g),
                               0u, 0u);
       ++nskew;
     }
@@ -1456,7 +1458,7 @@ __device__ __forceinline__ RunRow run_row(const SpreadArgs &a, uint32_t pos) {
 // DNS: the run's other-key constraint is DoNotSchedule (a template
 // parameter: the ScheduleAnyway runs compile without the blocking code,
 // which costs them registers and ~1k cycles per pod)
-template <bool DNS>
+template <bool DNS, bool GF = false>
 __global__ __launch_bounds__(RUN_THREADS) void replica_run_kernel(SpreadArgs a, ReplicaArgs r) {
   __shared__ SpreadDev s_sd[MAX_SPREAD];
   __shared__ Totals s_tot;
@@ -1801,7 +1803,7 @@ __global__ __launch_bounds__(RUN_THREADS) void replica_run_kernel(SpreadArgs a, 
         // the next pod's view of the node first (its S and Fit: the long
         // binary64 chain), then the stores nothing in the run reads
         const NodeRegs g = make_regs_inv(w.ac, w.am, w.rc, w.rm, w.zc, w.zm, w.ap, w.np, slot, ic, im);
-        const uint32_t S = (uint32_t)a.w.fit * (uint32_t)score_la(p, g) + (uint32_t)a.w.ba * (uint32_t)score_ba(p, g) + stat;
+        const uint32_t S = (uint32_t)a.w.fit * (uint32_t)score_fit<GF>(p, g, a.fs) + (uint32_t)a.w.ba * (uint32_t)score_ba(p, g) + stat;
         const bool fit_lost = filter<false>(p, a.clauses, g, NodeExt{}) != ST_FEASIBLE;
         // own hostname count, its domain's count
         if (inc_h && (code & RK_HK_NONE) != RK_HK_NONE) {
@@ -1974,12 +1976,16 @@ hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_
     // (the probe instantiation holds half the VGPRs: two workgroups per CU)
     const uint32_t pblocks = std::max<uint32_t>(
         1, std::min<uint32_t>((a.npos + SP_THREADS - 1) / SP_THREADS, 2u * (uint32_t)SPREAD_MAX_BLOCKS));
+    // the probe pass writes win_st only: no score, one variant
     if (passes & SPL_AFF) spread_filter_kernel<true, true><<<pblocks, SP_THREADS, 0, st>>>(pr);
     else spread_filter_kernel<false, true><<<pblocks, SP_THREADS, 0, st>>>(pr);
     spread_wcount_kernel<<<(a.nslots + WIN_CHUNK - 1) / WIN_CHUNK, WIN_CHUNK / 16, 0, st>>>(a);
     spread_window_kernel<<<1, WIN_THREADS, 0, st>>>(a);
   }
-  if (passes & SPL_AFF) spread_filter_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
+  if (a.fit_general) {
+    if (passes & SPL_AFF) spread_filter_kernel<true, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_filter_kernel<false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  } else if (passes & SPL_AFF) spread_filter_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
   else spread_filter_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
   if (passes & SPL_SCORE) spread_score_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
   spread_select_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
@@ -2003,14 +2009,22 @@ hipError_t launch_replica_run(const SpreadArgs &a, const ReplicaArgs &r, void *s
   // a DoNotSchedule constraint: its domain counts and minimum first, as the chain
   if (passes & SPL_PREP) spread_prep_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
   if (passes & SPL_MIN) spread_min_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
-  spread_filter_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
-  replica_keys_kernel<<<blocks, SP_THREADS, 0, st>>>(a, r);
+  if (a.fit_general) {
+    spread_filter_kernel<false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    replica_keys_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a, r);
+  } else {
+    spread_filter_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
+    replica_keys_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a, r);
+  }
   size_t bytes = sort_tmp_bytes;
   if ((e = launch_sort_pairs(r.keys, r.sorted, r.val, r.sval, r.nslots, 20 + r.s_bits, sort_tmp, &bytes, st)) !=
       hipSuccess)
     return e;
   replica_groups_kernel<<<blocks, SP_THREADS, 0, st>>>(a, r);
-  if (passes & SPL_MIN) replica_run_kernel<true><<<1, RUN_THREADS, 0, st>>>(a, r);  // DoNotSchedule (SPL_MIN)
+  if (a.fit_general) {
+    if (passes & SPL_MIN) replica_run_kernel<true, true><<<1, RUN_THREADS, 0, st>>>(a, r);
+    else replica_run_kernel<false, true><<<1, RUN_THREADS, 0, st>>>(a, r);
+  } else if (passes & SPL_MIN) replica_run_kernel<true><<<1, RUN_THREADS, 0, st>>>(a, r);  // DoNotSchedule (SPL_MIN)
   else replica_run_kernel<false><<<1, RUN_THREADS, 0, st>>>(a, r);
   return launch_spread_reset(a, st);
 }

@@ -312,6 +312,13 @@ EXPECTED_SIZES = {
     "ks_node_score": 56, "ks_node_state": 56, "ks_config": 124, "ks_pod_affinity_term": 96, "ks_stats": 112, "ks_label_selector": 32,
     "ks_spread_constraint": 72,
 }
+class KsFitStrategy(C.Structure):  # ks_fit_strategy (ks_set_fit_strategy / ks_get_fit_strategy)
+    _fields_ = [("type", C.c_int32), ("weight_cpu", C.c_int32), ("weight_memory", C.c_int32), ("_pad", C.c_int32)]
+
+
+FIT_LEAST_ALLOCATED, FIT_MOST_ALLOCATED = 0, 1
+FIT_TYPES = {"LeastAllocated": FIT_LEAST_ALLOCATED, "MostAllocated": FIT_MOST_ALLOCATED}
+
 STRUCTS = {
     "ks_label": KsLabel, "ks_taint": KsTaint, "ks_toleration": KsToleration, "ks_node": KsNode,
     "ks_container": KsContainer, "ks_requirement": KsRequirement, "ks_term": KsTerm,
@@ -329,6 +336,7 @@ KSCHED_SYMBOLS = [
     "ks_comm_init", "ks_comm_allreduce_max", "ks_get_stats", "ks_reset_stats", "ks_set_timing",
     "ks_debug_counters", "ks_debug_set_profile", "ks_debug_resolve_profile", "ks_debug_round_record", "ks_set_sync_timeout", "ks_debug_stall", "ks_batch_marks",
     "ks_debug_runs_started", "ks_next_start_index", "ks_debug_sweep_geometry",
+    "ks_set_fit_strategy", "ks_get_fit_strategy",
 ]
 KSGATHER_SYMBOLS = [
     "ksg_open", "ksg_close", "ksg_set_members", "ksg_record_and_wait", "ksg_pending", "ksg_fnv1_32", "ksg_target_index",
@@ -401,6 +409,8 @@ def ksched_lib() -> C.CDLL:
     L.ks_get_stats.argtypes = [vp, P(KsStats)]
     L.ks_reset_stats.argtypes = [vp]
     L.ks_set_timing.argtypes = [vp, C.c_int32]
+    L.ks_set_fit_strategy.argtypes = [vp, P(KsFitStrategy)]
+    L.ks_get_fit_strategy.argtypes = [vp, P(KsFitStrategy)]
     L.ks_debug_counters.argtypes = [vp, P(C.c_uint64)]
     L.ks_debug_sweep_geometry.argtypes = [vp, C.c_int32, P(C.c_uint64)]
     L.ks_debug_set_profile.argtypes = [vp, C.c_int32]

@@ -118,11 +118,14 @@ class Scheduler:
     def __init__(self, node_capacity: int, *, device: int = 0, pods_per_round: int = 256, topk: int = 0,
                  nodes_per_lane: int = 4, world_size: int = 1, rank: int = 0, virtual_shards: int = 1,
                  weights: Optional[Dict[str, int]] = None, options: Optional[Dict[str, int]] = None,
-                 percentage_of_nodes_to_score: int = 100):
+                 percentage_of_nodes_to_score: int = 100, fit_strategy: str = "LeastAllocated",
+                 fit_resource_weights: Optional[Dict[str, int]] = None):
         """options: ks_config execution options by field name (_abi.OPTION_FIELDS),
         e.g. {"resolve_mode": _abi.RESOLVE_SERIAL, "dedup_identical_pods": 0};
         none of them changes a result.  percentage_of_nodes_to_score: the
-        profile's percentageOfNodesToScore (ksched.h; below 100 one shard only)."""
+        profile's percentageOfNodesToScore (ksched.h; below 100 one shard only).
+        fit_strategy / fit_resource_weights: NodeResourcesFitArgs.scoringStrategy
+        (set_fit_strategy)."""
         self.lib = _abi.ksched_lib()
         cfg = _abi.KsConfig()
         self.lib.ks_config_default(C.byref(cfg))
@@ -157,6 +160,33 @@ class Scheduler:
         self.names: Dict[int, str] = {}
         self.slots: Dict[str, int] = {}
         self.slot_gen: Dict[int, int] = {}  # last NodeInfo.Generation applied per slot (snapshot_update)
+        if fit_strategy != "LeastAllocated" or fit_resource_weights is not None:
+            try:
+                self.set_fit_strategy(fit_strategy, fit_resource_weights)
+            except Exception:
+                self.close()
+                raise
+
+    def set_fit_strategy(self, strategy: str = "LeastAllocated", resource_weights: Optional[Dict[str, int]] = None):
+        """NodeResourcesFitArgs.scoringStrategy: type "LeastAllocated" or
+        "MostAllocated", resources {"cpu": w, "memory": w} (1..100 each; a
+        resource left out is not scored; default both 1).  Applies to every
+        batch run after the call (ks_set_fit_strategy)."""
+        if strategy not in _abi.FIT_TYPES:
+            raise ValueError(f"unknown NodeResourcesFit scoring strategy {strategy}")
+        w = {"cpu": 1, "memory": 1} if resource_weights is None else dict(resource_weights)
+        unknown = set(w) - {"cpu", "memory"}
+        if unknown:
+            raise ValueError(f"NodeResourcesFit scores cpu and memory only, not {sorted(unknown)}")
+        fs = _abi.KsFitStrategy(_abi.FIT_TYPES[strategy], int(w.get("cpu", 0)), int(w.get("memory", 0)), 0)
+        self._ok(self.lib.ks_set_fit_strategy(self.ctx, C.byref(fs)))
+
+    def get_fit_strategy(self):
+        """(strategy name, {"cpu": w, "memory": w}) in force."""
+        fs = _abi.KsFitStrategy()
+        self._ok(self.lib.ks_get_fit_strategy(self.ctx, C.byref(fs)))
+        name = next(k for k, v in _abi.FIT_TYPES.items() if v == fs.type)
+        return name, {"cpu": int(fs.weight_cpu), "memory": int(fs.weight_memory)}
 
     def next_start_index(self) -> int:
         """Scheduler.nextStartNodeIndex (percentageOfNodesToScore < 100)."""

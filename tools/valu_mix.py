@@ -90,7 +90,7 @@ def kernels(lines):
     for ln in lines:
         m = re.match(r"^[0-9a-f]+ <(.*)>:$", ln)
         if m:
-            cur = m.group(1) if "sweep_kernel" in m.group(1) else None
+            cur = m.group(1) if "sweep_kernel" in m.group(1) and not general_variant(m.group(1)) else None
             if cur:
                 out[cur] = []
             continue
@@ -119,6 +119,12 @@ def pod_loop(ins):
         if best is None or a - t > best[1] - best[0]:
             best = (t, a + 4)
     return best
+
+
+def general_variant(mangled: str) -> bool:
+    """sweep_kernel<NPL, EXT, LWU, GF = true>: the instances of a non-default
+    NodeResourcesFit strategy, which bench.py never runs."""
+    return re.search(r"sweep_kernelILi\d+ELb\dELi\d+ELb1EE", mangled) is not None
 
 
 def template_args(mangled: str) -> str:
