@@ -658,8 +658,8 @@ ks_status ks_debug_runs_started(ks_ctx *ctx, uint64_t *out);
 /* 1 = time sweep / resolve launches with HIP events (every KS_TIMING_EVERY-th
  * round, default 8; sweep_evals counts the timed launches' share), 0 = off. */
 ks_status ks_set_timing(ks_ctx *ctx, int32_t enabled);
-/* NodeResourcesFitArgs.scoringStrategy: LeastAllocated or MostAllocated over
- * {cpu, memory} with per-resource weights (upstream v1.31.3
+/* NodeResourcesFitArgs.scoringStrategy: LeastAllocated, MostAllocated or
+ * RequestedToCapacityRatio over {cpu, memory} with per-resource weights (upstream v1.31.3
  * noderesources/{least,most}_allocated.go, resource_allocation.go).  Per scored
  * resource with non-zero Allocatable, requested = the node's NonZeroRequested +
  * the pod's non-zero request:
@@ -678,16 +678,43 @@ ks_status ks_set_timing(ks_ctx *ctx, int32_t enabled);
  * default returns KS_ERR_UNSUPPORTED: the window's only reference is the
  * oracle's own schedule, which knows the default strategy alone, and nothing
  * ships here that a parity test does not pin.
- * RequestedToCapacityRatio and extended resources in the list: not modelled. */
-enum { KS_FIT_LEAST_ALLOCATED = 0, KS_FIT_MOST_ALLOCATED = 1 };
+ * Extended resources in the list: not modelled (the struct carries cpu and
+ * memory only).
+ *
+ * RequestedToCapacityRatio (requested_to_capacity_ratio.go, helper/shape_score.go)
+ * takes a shape besides the weights: 1..101 points {utilization 0..100, strictly
+ * increasing; score 0..10}.  Scores count x 10; raw(p) is the first point's
+ * score up to it, the last point's beyond it, and between two points
+ * y0 + (y1 - y0) * (p - x0) / (x1 - x0) in int64, whose division truncates toward
+ * zero.  Per listed resource with non-zero Allocatable the score is
+ * raw(requested > capacity ? 100 : requested * 100 / capacity); the node score is
+ * math.Round(sum(score x weight) / sum(weight)) over the resources whose score
+ * is positive (half away from zero; 0 when none is).
+ * ks_set_fit_strategy_shape sets it (type KS_FIT_REQUESTED_TO_CAPACITY_RATIO;
+ * with another type and no shape it is ks_set_fit_strategy) under the rules
+ * above: it waits, applies to every batch run after it, and returns
+ * KS_ERR_UNSUPPORTED with percentage_of_nodes_to_score < 100.  KS_ERR_INVALID: a
+ * null or empty shape, more than 101 points, a utilization outside 0..100 or
+ * not strictly increasing, a score outside 0..10, the weights as above.
+ * ks_set_fit_strategy itself refuses the type (KS_ERR_INVALID): it has no shape.
+ * ks_get_fit_strategy reports the type in force; ks_get_fit_shape copies its
+ * shape (*n points; 0 under the other two types) and returns KS_ERR_INVALID,
+ * with *n set, when cap is below it.
+ * ks_fit_shape_table needs no context: it validates a shape and fills
+ * out[p] = raw(p) for p = 0..100, the table the kernels read. */
+enum { KS_FIT_LEAST_ALLOCATED = 0, KS_FIT_MOST_ALLOCATED = 1, KS_FIT_REQUESTED_TO_CAPACITY_RATIO = 2 };
 typedef struct {
   int32_t type;           /* KS_FIT_*                       */
   int32_t weight_cpu;     /* resources: {name: cpu, weight}    */
   int32_t weight_memory;  /* resources: {name: memory, weight} */
   int32_t _pad;
 } ks_fit_strategy;
+typedef struct { int32_t utilization, score; } ks_fit_shape_point;
 ks_status ks_set_fit_strategy(ks_ctx *ctx, const ks_fit_strategy *s);
 ks_status ks_get_fit_strategy(ks_ctx *ctx, ks_fit_strategy *out);
+ks_status ks_set_fit_strategy_shape(ks_ctx *ctx, const ks_fit_strategy *s, const ks_fit_shape_point *shape, uint32_t n);
+ks_status ks_get_fit_shape(ks_ctx *ctx, ks_fit_shape_point *out, uint32_t cap, uint32_t *n);
+ks_status ks_fit_shape_table(const ks_fit_shape_point *shape, uint32_t n, uint8_t out[101]);
 
 #ifdef __cplusplus
 }

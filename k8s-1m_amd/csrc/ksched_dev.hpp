@@ -4,6 +4,8 @@
 
 #include <stdint.h>
 
+#include "ksched_fit_shape.hpp"
+
 namespace ks {
 
 // ------------------------------------------------------------------ limits
@@ -316,13 +318,13 @@ struct Weights {
 // weight of the resources whose allocatable is non-zero: floor(n / d) for
 // n <= 20000 is (2 n x rcp) >> 32 with rcp = ceil(2^31 / d), 0 for d == 0
 // (fit_weight_rcp; checked over the whole domain by tools/fit_check.cpp).
+// RequestedToCapacityRatio (GF == 2) takes the utilisation
+// MostAllocated computes through the shape table (ksched_fit_shape.hpp) and
+// rounds: its reciprocals are those of 2 d.
 struct FitParams {
-  uint32_t most;                       // 1 MostAllocated, 0 LeastAllocated
+  uint32_t most;                       // 0 LeastAllocated, else the utilisation: 1 MostAllocated, 2 RequestedToCapacityRatio
   uint32_t wc, wm;                     // resource weights, 0..100 (0: not listed)
-  uint32_t rcp_cpu, rcp_mem, rcp_both; // d = wc, wm, wc + wm
+  uint32_t rcp_cpu, rcp_mem, rcp_both; // d = wc, wm, wc + wm (RequestedToCapacityRatio: 2 d)
 };
-__host__ __device__ inline uint32_t fit_weight_rcp(uint32_t d) {
-  return d ? (uint32_t)(((1ull << 31) + d - 1) / d) : 0u;
-}
 
 }  // namespace ks

@@ -252,8 +252,8 @@ __device__ __forceinline__ uint32_t fit_resource(bool most, double lf100, double
   return r;
 }
 
-// NodeResourcesFit's score.  GF == false: {LeastAllocated, 1, 1}, the code
-// every default context runs.  GF == true: the context's strategy f
+// NodeResourcesFit's score.  GF == 0: {LeastAllocated, 1, 1}, the code
+// every default context runs.  GF == 1: the context's strategy f
 // (resource_allocation.go#score): sum of weight x resource score over the
 // resources with non-zero allocatable, divided by their summed weight by a
 // reciprocal multiply (FitParams); a zero weight sum gives n == 0 -> 0.
@@ -271,10 +271,49 @@ __device__ __forceinline__ int32_t score_fit_general(double nz100_cpu, double nz
   const uint32_t rcp = hc ? (hm ? rb : rc) : rm;
   return (int32_t)__umulhi(n << 1, rcp);
 }
-template <bool GF>
+
+// RequestedToCapacityRatio (GF == 2).  The shape table T[0..100]
+// (ksched_fit_shape.hpp) lives in LDS: each kernel variant that scores under it
+// copies the context's 128-byte device copy there once per workgroup
+// (fit_table_stage, then a barrier), so an evaluation costs two byte reads
+// from LDS -- 26 dwords in distinct banks -- and no global load.
+__device__ __forceinline__ uint32_t *fit_table_lds() {
+  __shared__ uint32_t s_fit_table[FIT_TABLE_WORDS];
+  return s_fit_table;
+}
+__device__ __forceinline__ void fit_table_stage(const uint32_t *table) {
+  if (threadIdx.x < FIT_TABLE_WORDS) fit_table_lds()[threadIdx.x] = table[threadIdx.x];
+}
+// requested_to_capacity_ratio.go: per resource the utilisation MostAllocated
+// computes (requested > capacity clamps to 100) goes through the table; a
+// resource with zero Allocatable has u == 0 yet does not take part (T[0] may be
+// positive), so it is masked before the sum.  T: LDS (fit_table_lds) or, in the
+// score dumps, the device copy itself.  u <= 100 by the clamp; the min keeps a
+// corrupt node row inside the 128 bytes.
+__device__ __forceinline__ int32_t score_fit_rtcr(double nz100_cpu, double nz100_mem, const NodeRegs &r,
+                                                  const FitParams &f, const uint8_t *T) {
+  const uint32_t uc = min(fit_resource(true, r.lf100_cpu, nz100_cpu, r.acpu_d, r.inv_cpu), 100u);
+  const uint32_t um = min(fit_resource(true, r.lf100_mem, nz100_mem, r.amem_d, r.inv_mem), 100u);
+  const uint32_t tc = r.inv_cpu != 0.0 ? (uint32_t)T[uc] : 0u, tm = r.inv_mem != 0.0 ? (uint32_t)T[um] : 0u;
+  // the reciprocals as scalar registers, as in score_fit_general
+  const uint32_t rb = __builtin_amdgcn_readfirstlane(f.rcp_both), rc = __builtin_amdgcn_readfirstlane(f.rcp_cpu),
+                 rm = __builtin_amdgcn_readfirstlane(f.rcp_mem);
+  return (int32_t)fit_rtcr_node_score(tc, tm, f.wc, f.wm, rc, rm, rb);
+}
+
+// GF: 0 the default strategy, 1 LeastAllocated / MostAllocated with weights,
+// 2 RequestedToCapacityRatio (the launchers pass RoundArgs::fit_general)
+template <int GF>
+__device__ __forceinline__ int32_t score_fit_nz(double nz100_cpu, double nz100_mem, const NodeRegs &r,
+                                                const FitParams &f) {
+  static_assert(GF == 1 || GF == 2, "the default strategy scores a PodDev (score_la)");
+  if constexpr (GF == 2) return score_fit_rtcr(nz100_cpu, nz100_mem, r, f, (const uint8_t *)fit_table_lds());
+  else return score_fit_general(nz100_cpu, nz100_mem, r, f);
+}
+template <int GF>
 __device__ __forceinline__ int32_t score_fit(const PodDev &p, const NodeRegs &r, const FitParams &f) {
-  if constexpr (!GF) return score_la(p, r);
-  else return score_fit_general(p.nz100_cpu, p.nz100_mem, r, f);
+  if constexpr (GF == 0) return score_la(p, r);
+  else return score_fit_nz<GF>(p.nz100_cpu, p.nz100_mem, r, f);
 }
 
 // RN(a / b) from y = RN(1 / b): q0 = RN(a y) is within one ulp of a/b, the
@@ -316,7 +355,7 @@ __device__ __forceinline__ int64_t normalize(int64_t raw, int64_t mx, bool rever
 
 // Plugin scores are in [0, 100] and ks_open caps the weights at 10000, so the
 // weighted sum fits 23 bits: 24-bit multiplies, 32-bit adds.
-template <bool EXT, bool GF>
+template <bool EXT, int GF>
 __device__ __forceinline__ int32_t total_score(const PodDev &p, const uint64_t *clauses, const NodeRegs &r,
                                                const NodeExt &e, const Weights &w, const FitParams &fs,
                                                int64_t tt_max, int64_t na_max) {

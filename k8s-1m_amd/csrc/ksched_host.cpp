@@ -403,7 +403,8 @@ struct ks_ctx {
   // the launchers take the kernels' general variants with fit_params
   ks_fit_strategy fit{KS_FIT_LEAST_ALLOCATED, 1, 1, 0};
   FitParams fit_params{0, 1, 1, fit_weight_rcp(1), fit_weight_rcp(1), fit_weight_rcp(2)};
-  uint32_t fit_general = 0;
+  uint32_t fit_general = 0;  // 1 LeastAllocated / MostAllocated, 2 RequestedToCapacityRatio
+  std::vector<ks_fit_shape_point> fit_shape;  // the shape in force under RequestedToCapacityRatio (else empty)
   // Execution options from ks_config (ks_open), per context, so one process
   // can open contexts with different settings (tests do).
   bool early_fix = true;
@@ -457,6 +458,7 @@ struct ks_ctx {
   size_t brec_bytes = 0;          // per parity
   uint64_t *d_srec = nullptr, *d_frec = nullptr;
   uint64_t *d_counters = nullptr;
+  uint32_t *d_fit_table = nullptr;  // RequestedToCapacityRatio: the shape table T[0..100], FIT_TABLE_WORDS dwords
   CandRow *d_crow = nullptr;
   CandExt *d_cext = nullptr;
   // pipeline state: [0,1] sweep start, [2,3] actual start, [4,5] carry counts (by parity)
@@ -2929,6 +2931,7 @@ ks_status enqueue_round(ks_ctx *c, ks_batch *b, uint32_t k, uint32_t end) {
                 c->cfg.weight_image};
   a.fs = c->fit_params;
   a.fit_general = c->fit_general;
+  a.fit_table = c->d_fit_table;
   if ((size_t)nloc * c->P * bmax * sizeof(BlockRec) > c->brec_bytes)
     return c->fail(KS_ERR_INVALID, "block record buffer too small");
 
@@ -3659,7 +3662,7 @@ static ks_status open_device(ks_ctx *x, const ks_config *cfg) {
       (st = dalloc(x, &x->d_pstat, (size_t)x->P)) || (st = dalloc(x, &x->d_fix, 2 * MAX_P + MAX_P / MAX_PG)) ||
       (st = dalloc(x, &x->d_dedup, 2 * (2 * (size_t)MAX_P + 4))) ||
       (st = dalloc(x, &x->d_pipe, 8)) || (st = dalloc(x, &x->d_flags, 8)) || (st = dalloc(x, &x->d_carry, 2 * (size_t)MAX_P)) ||
-      (st = dalloc(x, &x->d_counters, 32)))
+      (st = dalloc(x, &x->d_counters, 32)) || (st = dalloc(x, &x->d_fit_table, FIT_TABLE_WORDS)))
     return st;
   if ((st = xfer_begin(x, x->S * sizeof(Shard) + (size_t)x->cap * 4 + 1024, 0)) ||
       (st = h2d(x, x->d_shards, x->shards.data(), x->S * sizeof(Shard))) ||
@@ -4546,6 +4549,7 @@ SpreadArgs spread_args(ks_ctx *c) {
                  c->cfg.weight_image};
   sa.fs = c->fit_params;
   sa.fit_general = c->fit_general;
+  sa.fit_table = c->d_fit_table;
   sa.w_pts = c->cfg.weight_topology_spread;
   sa.w_ipa = c->cfg.weight_inter_pod_affinity;
   sa.evaluated = c->n_present;
@@ -4617,6 +4621,7 @@ ks_status ks_plugin_scores(ks_ctx *c, const ks_pod *pod, ks_node_score *out) {
                 c->cfg.weight_image};
   a.fs = c->fit_params;
   a.fit_general = c->fit_general;
+  a.fit_table = c->d_fit_table;
   a.slot_pos = c->d_slot_pos;
   std::vector<int32_t> raw((size_t)c->cap * 10);
   const size_t bytes = sizeof(PodDev) + cl.w.size() * 8 + 8 + raw.size() * 4 + 2048;
@@ -4873,6 +4878,47 @@ ks_status ks_set_fit_strategy(ks_ctx *c, const ks_fit_strategy *s) {
   c->fit_params = FitParams{s->type == KS_FIT_MOST_ALLOCATED ? 1u : 0u, wc, wm, fit_weight_rcp(wc), fit_weight_rcp(wm),
                             fit_weight_rcp(wc + wm)};
   c->fit_general = general ? 1u : 0u;
+  c->fit_shape.clear();
+  return KS_OK;
+}
+
+ks_status ks_fit_shape_table(const ks_fit_shape_point *shape, uint32_t n, uint8_t out[101]) {
+  return fit_shape_table(shape, n, out) ? KS_OK : KS_ERR_INVALID;
+}
+
+ks_status ks_set_fit_strategy_shape(ks_ctx *c, const ks_fit_strategy *s, const ks_fit_shape_point *shape, uint32_t n) {
+  if (!c || !s) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  if (s->type != KS_FIT_REQUESTED_TO_CAPACITY_RATIO) return shape || n ? KS_ERR_INVALID : ks_set_fit_strategy(c, s);
+  if (s->weight_cpu < 0 || s->weight_cpu > 100 || s->weight_memory < 0 || s->weight_memory > 100 ||
+      (s->weight_cpu == 0 && s->weight_memory == 0))
+    return KS_ERR_INVALID;
+  // T[0..100], the tail of the 128-byte copy repeating T[100]
+  uint8_t tab[FIT_TABLE_WORDS * 4];
+  if (!fit_shape_table(shape, n, tab)) return KS_ERR_INVALID;
+  for (uint32_t i = FIT_TABLE_N; i < sizeof tab; ++i) tab[i] = tab[FIT_TABLE_N - 1];
+  // as ks_set_fit_strategy: no reference for the window under another strategy
+  if (c->pct != 100) return KS_ERR_UNSUPPORTED;
+  // no batch runs (drained above): the device copy has no reader
+  ks_status st;
+  if ((st = xfer_begin(c, 1024, 0)) || (st = h2d(c, c->d_fit_table, tab, sizeof tab)) || (st = xfer_sync(c))) return st;
+  std::lock_guard<std::mutex> g(c->mu);
+  c->fit = ks_fit_strategy{s->type, s->weight_cpu, s->weight_memory, 0};
+  const uint32_t wc = (uint32_t)s->weight_cpu, wm = (uint32_t)s->weight_memory;
+  // math.Round(n / d) = floor((2 n + d) / (2 d)): the reciprocals of 2 d (fit_rtcr_node_score)
+  c->fit_params = FitParams{2u, wc, wm, fit_weight_rcp(2 * wc), fit_weight_rcp(2 * wm), fit_weight_rcp(2 * (wc + wm))};
+  c->fit_general = 2u;
+  c->fit_shape.assign(shape, shape + n);
+  return KS_OK;
+}
+
+ks_status ks_get_fit_shape(ks_ctx *c, ks_fit_shape_point *out, uint32_t cap, uint32_t *n) {
+  if (!c || !n || (!out && cap)) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  std::lock_guard<std::mutex> g(c->mu);
+  *n = (uint32_t)c->fit_shape.size();  // 0: the strategy in force has no shape
+  if (cap < *n) return KS_ERR_INVALID;
+  std::copy(c->fit_shape.begin(), c->fit_shape.end(), out);
   return KS_OK;
 }
 

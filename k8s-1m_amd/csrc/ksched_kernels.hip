@@ -177,9 +177,10 @@ __device__ __forceinline__ uint32_t normalize_inv(uint32_t raw, double inv) {
 constexpr uint32_t KEY32_POS_BITS = 9, KEY32_POS_MASK = (1u << KEY32_POS_BITS) - 1;
 
 // GF: the NodeResourcesFit score under the context's strategy (score_fit,
-// a.fs) instead of {LeastAllocated, 1, 1}: instances of
-// their own, so the default strategy's kernels are the code they were.
-template <int NPL, bool EXT, int LWU = LW, bool GF = false>
+// a.fs) instead of {LeastAllocated, 1, 1}: 1 LeastAllocated / MostAllocated
+// with weights, 2 RequestedToCapacityRatio (§5.10).  Instances
+// of their own, so the default strategy's kernels are the code they were.
+template <int NPL, bool EXT, int LWU = LW, int GF = 0>
 // EXT with 2 nodes per lane: 5 waves per SIMD (91 VGPRs) runs the C4 sweep
 // 5 % faster than 4 (103 VGPRs); 6 waves spill 72 B; the resource-only
 // kernel at 5 waves spills 20 B and measured 9 % slower (kept at 4).  The
@@ -210,6 +211,10 @@ void sweep_kernel(RoundArgs a) {
   if (dedup) p1 = min(p1, start + uniform_u32(*a.nuniq));
   if (p0 >= p1 || blockIdx.x * NW >= kwaves) return;
   if (fix && uniform_u32(a.fix_group[blockIdx.y]) == 0) return;
+  if constexpr (GF == 2) {  // the shape table: one load per workgroup, none in the pod loop
+    fit_table_stage(a.fit_table);
+    __syncthreads();  // (the returns above are the whole workgroup's)
+  }
 
   NodeRegs nr[NPL];
   NodeExt ne[EXT ? NPL : 1];
@@ -791,7 +796,7 @@ __device__ __forceinline__ uint32_t count_greater(const uint64_t *v, uint32_t n,
 }
 
 
-template <bool EXT, int PATCH_THREADS, bool GF = false>
+template <bool EXT, int PATCH_THREADS, int GF = 0>
 __global__ __launch_bounds__(PATCH_THREADS) void patch_kernel(RoundArgs a) {
   static_assert(PATCH_THREADS >= MAX_P, "one thread per carried node");
   constexpr int NW = PATCH_THREADS / WAVE;
@@ -821,6 +826,7 @@ __global__ __launch_bounds__(PATCH_THREADS) void patch_kernel(RoundArgs a) {
     na_max = a.norm_max[2 * r + 1];
   }
   for (uint32_t i = tid; i < PHASH; i += PATCH_THREADS) s_hkey[i] = 0;
+  if constexpr (GF == 2) fit_table_stage(a.fit_table);  // the shape table, before the barrier
   __syncthreads();
 
   // (1) carried node tid: its row at the sweep (rc0 / rm0 / np0) and live.
@@ -1143,6 +1149,10 @@ __global__ void dump_max_kernel(DumpArgs a) {
 }
 
 __global__ void dump_scores_kernel(DumpArgs a) {
+  if (a.fit_general == 2) {  // RequestedToCapacityRatio's shape table, by every thread's workgroup
+    fit_table_stage(a.fit_table);
+    __syncthreads();
+  }
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.nslots) return;
   const uint32_t pos = a.slot_pos[i];
@@ -1159,7 +1169,7 @@ __global__ void dump_scores_kernel(DumpArgs a) {
   o[0] = st;
   if (st != ST_FEASIBLE) return;
   const int64_t tt_max = a.norm_max[0], na_max = a.norm_max[1];
-  o[1] = a.fit_general ? score_fit<true>(p, r, a.fs) : score_fit<false>(p, r, a.fs);
+  o[1] = a.fit_general == 2 ? score_fit<2>(p, r, a.fs) : a.fit_general ? score_fit<1>(p, r, a.fs) : score_fit<0>(p, r, a.fs);
   o[2] = (int32_t)score_ba(p, r);
   const int64_t tr = (p.flags & PF_TT) ? taint_raw(p, e) : 0;
   o[3] = (int32_t)tr;
@@ -1168,8 +1178,9 @@ __global__ void dump_scores_kernel(DumpArgs a) {
   o[5] = (int32_t)nr;
   o[6] = (p.flags & PF_HAS_PREF) ? (int32_t)normalize(nr, (p.flags & PF_NA) ? na_max : 0, false) : 0;
   o[7] = 0;
-  const int64_t tot = a.fit_general ? total_score<true, true>(p, a.clauses, r, e, a.w, a.fs, tt_max, na_max)
-                                    : total_score<true, false>(p, a.clauses, r, e, a.w, a.fs, tt_max, na_max);
+  const int64_t tot = a.fit_general == 2 ? total_score<true, 2>(p, a.clauses, r, e, a.w, a.fs, tt_max, na_max)
+                      : a.fit_general    ? total_score<true, 1>(p, a.clauses, r, e, a.w, a.fs, tt_max, na_max)
+                                         : total_score<true, 0>(p, a.clauses, r, e, a.w, a.fs, tt_max, na_max);
   o[8] = (int32_t)(tot & 0xFFFFFFFF);
   o[9] = (int32_t)(tot >> 32);
 }
@@ -1187,31 +1198,36 @@ hipError_t launch_norm_check(const RoundArgs &a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// the sweep's general variants (GF 1 or 2), by the default's geometry
+template <int GF>
+static hipError_t launch_sweep_fit(const RoundArgs &a, bool ext, dim3 g, hipStream_t st) {
+  if (ext) {
+    // label words in use (dictionary size): 1, 2 or 4 words per node are read
+    const uint32_t lwu = sweep_label_words(a.npl, a.t.lw);
+    if (a.npl == 2) {
+      if (lwu == 1) sweep_kernel<2, true, 1, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+      else if (lwu == 2) sweep_kernel<2, true, 2, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+      else sweep_kernel<2, true, 4, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+    } else if (a.npl == 4) {
+      if (lwu == 1) sweep_kernel<4, true, 1, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+      else if (lwu == 2) sweep_kernel<4, true, 2, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+      else sweep_kernel<4, true, 4, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+    } else {
+      sweep_kernel<8, true, 4, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+    }
+  } else {
+    if (a.npl == 2) sweep_kernel<2, false, LW, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+    else if (a.npl == 4) sweep_kernel<4, false, LW, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+    else sweep_kernel<8, false, LW, GF><<<g, SWEEP_THREADS, 0, st>>>(a);
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_sweep(const RoundArgs &a, bool ext, uint32_t nblocks, uint32_t ngroups, uint32_t nshards,
                         hipStream_t st) {
   dim3 g(nblocks, ngroups, nshards);
-  if (a.fit_general) {
-    if (ext) {
-      // label words in use (dictionary size): 1, 2 or 4 words per node are read
-      const uint32_t lwu = sweep_label_words(a.npl, a.t.lw);
-      if (a.npl == 2) {
-        if (lwu == 1) sweep_kernel<2, true, 1, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-        else if (lwu == 2) sweep_kernel<2, true, 2, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-        else sweep_kernel<2, true, 4, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-      } else if (a.npl == 4) {
-        if (lwu == 1) sweep_kernel<4, true, 1, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-        else if (lwu == 2) sweep_kernel<4, true, 2, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-        else sweep_kernel<4, true, 4, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-      } else {
-        sweep_kernel<8, true, 4, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-      }
-    } else {
-      if (a.npl == 2) sweep_kernel<2, false, LW, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-      else if (a.npl == 4) sweep_kernel<4, false, LW, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-      else sweep_kernel<8, false, LW, true><<<g, SWEEP_THREADS, 0, st>>>(a);
-    }
-    return hipGetLastError();
-  }
+  if (a.fit_general == 2) return launch_sweep_fit<2>(a, ext, g, st);
+  if (a.fit_general) return launch_sweep_fit<1>(a, ext, g, st);
   if (ext) {
     // label words in use (dictionary size): 1, 2 or 4 words per node are read
     const uint32_t lwu = sweep_label_words(a.npl, a.t.lw);
@@ -1265,17 +1281,21 @@ hipError_t launch_writeback(const NodeTable &t, const CarryRec *carry, const uin
   return hipGetLastError();
 }
 
-hipError_t launch_patch(const RoundArgs &a, bool ext, hipStream_t st) {
-  if (a.fit_general) {
-    if (a.K <= (uint32_t)MAX_P) {
-      if (ext) patch_kernel<true, MAX_P, true><<<a.P, MAX_P, 0, st>>>(a);
-      else patch_kernel<false, MAX_P, true><<<a.P, MAX_P, 0, st>>>(a);
-    } else {
-      if (ext) patch_kernel<true, MAX_K, true><<<a.P, MAX_K, 0, st>>>(a);
-      else patch_kernel<false, MAX_K, true><<<a.P, MAX_K, 0, st>>>(a);
-    }
-    return hipGetLastError();
+template <int GF>
+static hipError_t launch_patch_fit(const RoundArgs &a, bool ext, hipStream_t st) {
+  if (a.K <= (uint32_t)MAX_P) {
+    if (ext) patch_kernel<true, MAX_P, GF><<<a.P, MAX_P, 0, st>>>(a);
+    else patch_kernel<false, MAX_P, GF><<<a.P, MAX_P, 0, st>>>(a);
+  } else {
+    if (ext) patch_kernel<true, MAX_K, GF><<<a.P, MAX_K, 0, st>>>(a);
+    else patch_kernel<false, MAX_K, GF><<<a.P, MAX_K, 0, st>>>(a);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_patch(const RoundArgs &a, bool ext, hipStream_t st) {
+  if (a.fit_general == 2) return launch_patch_fit<2>(a, ext, st);
+  if (a.fit_general) return launch_patch_fit<1>(a, ext, st);
   if (a.K <= (uint32_t)MAX_P) {
     if (ext) patch_kernel<true, MAX_P><<<a.P, MAX_P, 0, st>>>(a);
     else patch_kernel<false, MAX_P><<<a.P, MAX_P, 0, st>>>(a);

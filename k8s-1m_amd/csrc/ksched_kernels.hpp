@@ -95,7 +95,10 @@ struct RoundArgs {
                               // representative was; [2] counts representatives), [CTR_PAR_*]
   Weights w;
   FitParams fs;               // NodeResourcesFit strategy of the general kernel variants ...
-  uint32_t fit_general;       // ... which the launchers choose when set (not {LeastAllocated, 1, 1})
+  uint32_t fit_general;       // ... which the launchers choose when set (not {LeastAllocated, 1, 1}):
+                              // 1 LeastAllocated / MostAllocated, 2 RequestedToCapacityRatio
+  const uint32_t *fit_table;  // 2: the shape table T[0..100] as FIT_TABLE_WORDS dwords (each kernel stages it in
+                              // LDS; last, so the members above keep their kernel-argument offsets)
 };
 
 struct DumpArgs {
@@ -109,6 +112,7 @@ struct DumpArgs {
   Weights w;
   FitParams fs;
   uint32_t fit_general;
+  const uint32_t *fit_table;  // as RoundArgs::fit_table
 };
 
 // PodTopologySpread path (ksched_spread.hip): one pod per launch chain.
@@ -161,6 +165,7 @@ struct SpreadArgs {
   uint32_t nslots;
   uint32_t win_mode;
   int32_t pct;
+  const uint32_t *fit_table;  // as RoundArgs::fit_table
 };
 constexpr uint32_t WIN_WORDS = 4;
 

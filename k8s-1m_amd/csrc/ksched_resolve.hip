@@ -185,7 +185,7 @@ __device__ __forceinline__ XS px_static(const PX &x, const uint64_t *clauses, co
 // packed key of the pod on the row's live state (0: infeasible): key_q on
 // rnode_regs, with the resource-free score part ss (w_tt x 100 for a
 // resource-only pod)
-template <bool GF>
+template <int GF>
 __device__ __forceinline__ uint64_t pq_key_ss(const PQ &q, const CandRow &r, uint32_t slot, const Weights &w,
                                               const FitParams &fs, int32_t ss) {
   if (!pq_fit(q, r, r.rc, r.rm, r.np)) return 0;
@@ -205,8 +205,8 @@ __device__ __forceinline__ uint64_t pq_key_ss(const PQ &q, const CandRow &r, uin
   g.lashift = (ac && am) ? 1u : 0u;
   g.slot = slot;
   int32_t la;
-  if constexpr (GF) {
-    la = score_fit_general(q.zc, q.zm, g, fs);
+  if constexpr (GF != 0) {
+    la = score_fit_nz<GF>(q.zc, q.zm, g, fs);
   } else {
     la = (least_requested(g.lf100_cpu, q.zc, g.inv_cpu) + least_requested(g.lf100_mem, q.zm, g.inv_mem)) >> g.lashift;
   }
@@ -214,7 +214,7 @@ __device__ __forceinline__ uint64_t pq_key_ss(const PQ &q, const CandRow &r, uin
   const int32_t t = (int32_t)wmul((uint32_t)w.fit, (uint32_t)la) + (int32_t)wmul((uint32_t)w.ba, (uint32_t)ba) + ss;
   return pack_key(t, slot);
 }
-template <bool GF>
+template <int GF>
 __device__ __forceinline__ uint64_t pq_key(const PQ &q, const CandRow &r, uint32_t slot, const Weights &w,
                                            const FitParams &fs) {
   return pq_key_ss<GF>(q, r, slot, w, fs, w.tt * 100);
@@ -230,7 +230,7 @@ struct PairEval {
   int32_t lost;
   uint32_t at_lost;
 };
-template <bool EXT, bool GF>
+template <bool EXT, int GF>
 __device__ __forceinline__ PairEval pair_eval(const PQ &q, const PX *px, const uint64_t *clauses, const CandRow &r,
                                               const CandExt *cx, uint32_t slot, double rc0, double rm0, int32_t np0,
                                               const Weights &w, const FitParams &fs) {
@@ -375,7 +375,7 @@ __device__ __forceinline__ SerialLds<EXT, LIST_SPAN> *ser_lds() {
 // Returns true when it resolved the round (or found it wasted); false when
 // the serial commit must take it (RESOLVE_SERIAL, a serial stretch of
 // RESOLVE_AUTO, or a hand-over from this round)
-template <bool EXT, bool GF>
+template <bool EXT, int GF>
 __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
   constexpr int NC = EXT ? PNC_EXT : PNC;      // candidates gathered per chunk pod
   constexpr int NR = EXT ? PNR_EXT : PNR;      // ... whose rows are prefetched
@@ -615,8 +615,11 @@ __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
     // defaults of a request-less pod raise the key as the node fills (the
     // "only falls" above is LeastAllocated's): every listed node is followed
     // to its end, and the first rise sends the round to the passes; the
-    // closed form keeps the rounds whose keys stay flat
-    const bool check_all = q0.rc != 0.0 || q0.rm != 0.0 || (GF && a.fs.most);
+    // closed form keeps the rounds whose keys stay flat.
+    // RequestedToCapacityRatio (fs.most == 2) likewise: under a peaked shape
+    // a node's key rises and then falls as it fills, under any shape it moves
+    // with the non-zero defaults
+    const bool check_all = q0.rc != 0.0 || q0.rm != 0.0 || (GF != 0 && a.fs.most != 0);
     __syncthreads();
     if (s_ic[1] == 0) {
       const uint32_t nk = min(h0.nkeys, (uint32_t)MAX_K);
@@ -1336,27 +1339,39 @@ __device__ __forceinline__ bool resolve_parallel(const RoundArgs &a) {
 // commit's (RESOLVE_SERIAL, a serial stretch, a hand-over).  The two share
 // one LDS allocation (a union: each is within the CU's 160 KB on its own);
 // the serial commit reads nothing the parallel one wrote to LDS.
-// GF: under the general NodeResourcesFit strategy (RoundArgs::fs)
-template <bool EXT, int LIST_SPAN, bool GF = false>
+// GF: under a NodeResourcesFit strategy other than the default (RoundArgs::fs;
+// 1: DESIGN.md §5.9, 2: RequestedToCapacityRatio, §5.10)
+template <bool EXT, int LIST_SPAN, int GF = 0>
 __global__ __launch_bounds__(PR_THREADS) void resolve_kernel(RoundArgs a) {
   static_assert(PR_THREADS == RESOLVE_THREADS, "both commits run on one 1024-thread workgroup");
+  if constexpr (GF == 2) {
+    // the shape table beside the union, for both commits: no load in any of their loops
+    static_assert(RES_LDS_BYTES + FIT_TABLE_WORDS * sizeof(uint32_t) <= 160u * 1024u,
+                  "RequestedToCapacityRatio: the shape table fits the CU's LDS beside the commits' union");
+    fit_table_stage(a.fit_table);
+    __syncthreads();
+  }
   if (resolve_parallel<EXT, GF>(a)) return;
   __syncthreads();  // the parallel commit's last LDS reads, its hand-over writes (rmode)
   resolve_serial<EXT, LIST_SPAN, GF>(a);
 }
 
+template <int GF>
+static hipError_t launch_resolve_fit(const RoundArgs &a, bool ext, bool one, hipStream_t st) {
+  if (one) {
+    if (ext) resolve_kernel<true, LIST_SPAN_1, GF><<<1, PR_THREADS, 0, st>>>(a);
+    else resolve_kernel<false, LIST_SPAN_1, GF><<<1, PR_THREADS, 0, st>>>(a);
+  } else {
+    if (ext) resolve_kernel<true, LIST_SPAN_2, GF><<<1, PR_THREADS, 0, st>>>(a);
+    else resolve_kernel<false, LIST_SPAN_2, GF><<<1, PR_THREADS, 0, st>>>(a);
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_resolve(const RoundArgs &a, bool ext, hipStream_t st) {
   const bool one = a.K <= (uint32_t)(RES_LIST_WAVES * LIST_SPAN_1);
-  if (a.fit_general) {
-    if (one) {
-      if (ext) resolve_kernel<true, LIST_SPAN_1, true><<<1, PR_THREADS, 0, st>>>(a);
-      else resolve_kernel<false, LIST_SPAN_1, true><<<1, PR_THREADS, 0, st>>>(a);
-    } else {
-      if (ext) resolve_kernel<true, LIST_SPAN_2, true><<<1, PR_THREADS, 0, st>>>(a);
-      else resolve_kernel<false, LIST_SPAN_2, true><<<1, PR_THREADS, 0, st>>>(a);
-    }
-    return hipGetLastError();
-  }
+  if (a.fit_general == 2) return launch_resolve_fit<2>(a, ext, one, st);
+  if (a.fit_general) return launch_resolve_fit<1>(a, ext, one, st);
   if (one) {
     if (ext) resolve_kernel<true, LIST_SPAN_1><<<1, PR_THREADS, 0, st>>>(a);
     else resolve_kernel<false, LIST_SPAN_1><<<1, PR_THREADS, 0, st>>>(a);

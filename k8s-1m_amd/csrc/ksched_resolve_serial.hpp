@@ -122,7 +122,7 @@ __device__ __forceinline__ PodQ pod_q(const PodDev &p, const Weights &w) {
 __device__ __forceinline__ bool fit_q(const PodQ &q, const NodeRegs &g) {
   return (g.bits & 2u) && !(q.rq_c > g.free_cpu) && !(q.rq_m > g.free_mem);
 }
-template <bool GF>
+template <int GF>
 __device__ __forceinline__ uint64_t key_q(const PodDev &p, const PodQ &q, const NodeRegs &g, const FitParams &fs) {
   const int32_t t = wmul((uint32_t)q.wf, (uint32_t)score_fit<GF>(p, g, fs)) +
                     wmul((uint32_t)q.wb, (uint32_t)score_ba(p, g)) + q.cplus;
@@ -177,7 +177,7 @@ struct SerialLds {
 template <bool EXT, int LIST_SPAN>
 __device__ __forceinline__ SerialLds<EXT, LIST_SPAN> *ser_lds();
 
-template <bool EXT, int LIST_SPAN, bool GF>
+template <bool EXT, int LIST_SPAN, int GF>
 __device__ __forceinline__ void resolve_serial(const RoundArgs &a) {
   constexpr bool TWO = LIST_SPAN == 2 * WAVE;
 #define s_pod (ser_lds<EXT, LIST_SPAN>()->s_pod)

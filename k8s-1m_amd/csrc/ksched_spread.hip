@@ -529,8 +529,9 @@ constexpr int RF = NFILT + 2, R_FEAS = RF, R_IGN = RF + 1, R_TT = RF + 2, R_NA =
 // them keeps their prefetched values out of the registers of spread pods.
 // PROBE: the percentageOfNodesToScore probe pass (win_mode 1) -- the filter
 // chain only; as a template parameter the score work compiles away there
-// GF: NodeResourcesFit scored under the context's strategy (a.fs, score_fit)
-template <bool AFF, bool PROBE = false, bool GF = false>
+// GF: NodeResourcesFit scored under the context's strategy (a.fs, score_fit;
+// 1 LeastAllocated / MostAllocated with weights, 2 RequestedToCapacityRatio)
+template <bool AFF, bool PROBE = false, int GF = 0>
 __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a) {
   __shared__ uint32_t s_seen[SP_LDS / 32];
   __shared__ uint32_t s_h[SP_LDS];
@@ -544,6 +545,7 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
   stage_solo(a, p, s_solo);
   for (uint32_t i = threadIdx.x; i < SP_LDS / 32; i += SP_THREADS) s_seen[i] = 0;
   for (uint32_t i = threadIdx.x; i < SP_LDS; i += SP_THREADS) s_h[i] = 0;
+  if constexpr (GF == 2 && !PROBE) fit_table_stage(a.fit_table);  // RequestedToCapacityRatio's shape table
   __syncthreads();
   const SpreadDev *sd = s_solo.sd;
   const uint32_t n = s_solo.h.n_spread;
@@ -1048,6 +1050,9 @@ __global__ __launch_bounds__(WIN_THREADS) void spread_window_kernel(SpreadArgs a
 // argmax; ks_plugin_scores writes the per-node plugin scores instead.  The
 // domain scratch is cleared for the next pod (its last reader was the score
 // pass).
+// RT: the dump under RequestedToCapacityRatio, which reads the shape table's
+// device copy (an instance of its own: the scheduling path's stays as it was)
+template <bool RT = false>
 __global__ __launch_bounds__(SP_THREADS) void spread_select_kernel(SpreadArgs a) {
   __shared__ uint64_t s_r[SP_THREADS / WAVE];
   __shared__ SoloLds s_solo;
@@ -1096,7 +1101,8 @@ __global__ __launch_bounds__(SP_THREADS) void spread_select_kernel(SpreadArgs a)
       load_ext(a.t, pos, true, e);
       int32_t *o = a.dump + (size_t)slot * SPREAD_DUMP_WORDS;
       o[0] = ST_FEASIBLE;
-      o[1] = a.fit_general ? score_fit<true>(p, r, a.fs) : score_fit<false>(p, r, a.fs);
+      if constexpr (RT) o[1] = score_fit_rtcr(p.nz100_cpu, p.nz100_mem, r, a.fs, (const uint8_t *)a.fit_table);
+      else o[1] = a.fit_general ? score_fit<true>(p, r, a.fs) : score_fit<false>(p, r, a.fs);
       o[2] = score_ba(p, r);
       const int64_t tr = (p.flags & PF_TT) ? taint_raw(p, e) : 0;
       o[3] = (int32_t)tr;
@@ -1321,7 +1327,7 @@ __device__ __forceinline__ uint32_t run_static(const PodDev &p, const Weights &w
 }
 
 // Sort key of every position (~0: not feasible) after the run's filter pass.
-template <bool GF>
+template <int GF>
 __global__ __launch_bounds__(SP_THREADS) void replica_keys_kernel(SpreadArgs a, ReplicaArgs r) {
   __shared__ SpreadDev s_sd[MAX_SPREAD];
   __shared__ uint32_t s_max[2];
@@ -1333,6 +1339,7 @@ __global__ __launch_bounds__(SP_THREADS) void replica_keys_kernel(SpreadArgs a, 
     s_max[0] = t.tt_max;
     s_max[1] = t.na_max;
   }
+  if constexpr (GF == 2) fit_table_stage(a.fit_table);
   __syncthreads();
   const RunCons k = run_cons(s_sd, n);
   const int64_t tt_max = s_max[0], na_max = s_max[1];
@@ -1458,7 +1465,7 @@ __device__ __forceinline__ RunRow run_row(const SpreadArgs &a, uint32_t pos) {
 // DNS: the run's other-key constraint is DoNotSchedule (a template
 // parameter: the ScheduleAnyway runs compile without the blocking code,
 // which costs them registers and ~1k cycles per pod)
-template <bool DNS, bool GF = false>
+template <bool DNS, int GF = 0>
 __global__ __launch_bounds__(RUN_THREADS) void replica_run_kernel(SpreadArgs a, ReplicaArgs r) {
   __shared__ SpreadDev s_sd[MAX_SPREAD];
   __shared__ Totals s_tot;
@@ -1501,6 +1508,7 @@ __global__ __launch_bounds__(RUN_THREADS) void replica_run_kernel(SpreadArgs a, 
     s_ctl[8] = RK_DZ_NONE;
     s_dzmax = 0;
   }
+  if constexpr (GF == 2) fit_table_stage(a.fit_table);  // the shape table: no load in the pod loop
   __syncthreads();
   const RunCons k = run_cons(s_sd, n);
   const uint32_t G = s_ctl[0], F = s_tot.feasible;
@@ -1982,13 +1990,17 @@ hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_
     spread_wcount_kernel<<<(a.nslots + WIN_CHUNK - 1) / WIN_CHUNK, WIN_CHUNK / 16, 0, st>>>(a);
     spread_window_kernel<<<1, WIN_THREADS, 0, st>>>(a);
   }
-  if (a.fit_general) {
-    if (passes & SPL_AFF) spread_filter_kernel<true, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_filter_kernel<false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  if (a.fit_general == 2) {
+    if (passes & SPL_AFF) spread_filter_kernel<true, false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_filter_kernel<false, false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
+  } else if (a.fit_general) {
+    if (passes & SPL_AFF) spread_filter_kernel<true, false, 1><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_filter_kernel<false, false, 1><<<blocks, SP_THREADS, 0, st>>>(a);
   } else if (passes & SPL_AFF) spread_filter_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
   else spread_filter_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
   if (passes & SPL_SCORE) spread_score_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
-  spread_select_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
+  if (a.fit_general == 2 && a.dump) spread_select_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
+  else spread_select_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
   spread_commit_kernel<<<1, WAVE, 0, st>>>(a);
   return hipGetLastError();
 }
@@ -2009,21 +2021,27 @@ hipError_t launch_replica_run(const SpreadArgs &a, const ReplicaArgs &r, void *s
   // a DoNotSchedule constraint: its domain counts and minimum first, as the chain
   if (passes & SPL_PREP) spread_prep_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
   if (passes & SPL_MIN) spread_min_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
-  if (a.fit_general) {
-    spread_filter_kernel<false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    replica_keys_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a, r);
+  if (a.fit_general == 2) {
+    spread_filter_kernel<false, false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
+    replica_keys_kernel<2><<<blocks, SP_THREADS, 0, st>>>(a, r);
+  } else if (a.fit_general) {
+    spread_filter_kernel<false, false, 1><<<blocks, SP_THREADS, 0, st>>>(a);
+    replica_keys_kernel<1><<<blocks, SP_THREADS, 0, st>>>(a, r);
   } else {
     spread_filter_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
-    replica_keys_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a, r);
+    replica_keys_kernel<0><<<blocks, SP_THREADS, 0, st>>>(a, r);
   }
   size_t bytes = sort_tmp_bytes;
   if ((e = launch_sort_pairs(r.keys, r.sorted, r.val, r.sval, r.nslots, 20 + r.s_bits, sort_tmp, &bytes, st)) !=
       hipSuccess)
     return e;
   replica_groups_kernel<<<blocks, SP_THREADS, 0, st>>>(a, r);
-  if (a.fit_general) {
-    if (passes & SPL_MIN) replica_run_kernel<true, true><<<1, RUN_THREADS, 0, st>>>(a, r);
-    else replica_run_kernel<false, true><<<1, RUN_THREADS, 0, st>>>(a, r);
+  if (a.fit_general == 2) {
+    if (passes & SPL_MIN) replica_run_kernel<true, 2><<<1, RUN_THREADS, 0, st>>>(a, r);
+    else replica_run_kernel<false, 2><<<1, RUN_THREADS, 0, st>>>(a, r);
+  } else if (a.fit_general) {
+    if (passes & SPL_MIN) replica_run_kernel<true, 1><<<1, RUN_THREADS, 0, st>>>(a, r);
+    else replica_run_kernel<false, 1><<<1, RUN_THREADS, 0, st>>>(a, r);
   } else if (passes & SPL_MIN) replica_run_kernel<true><<<1, RUN_THREADS, 0, st>>>(a, r);  // DoNotSchedule (SPL_MIN)
   else replica_run_kernel<false><<<1, RUN_THREADS, 0, st>>>(a, r);
   return launch_spread_reset(a, st);

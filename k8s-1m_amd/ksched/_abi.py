@@ -316,8 +316,14 @@ class KsFitStrategy(C.Structure):  # ks_fit_strategy (ks_set_fit_strategy / ks_g
     _fields_ = [("type", C.c_int32), ("weight_cpu", C.c_int32), ("weight_memory", C.c_int32), ("_pad", C.c_int32)]
 
 
-FIT_LEAST_ALLOCATED, FIT_MOST_ALLOCATED = 0, 1
-FIT_TYPES = {"LeastAllocated": FIT_LEAST_ALLOCATED, "MostAllocated": FIT_MOST_ALLOCATED}
+class KsFitShapePoint(C.Structure):  # ks_fit_shape_point (ks_set_fit_strategy_shape / ks_get_fit_shape)
+    _fields_ = [("utilization", C.c_int32), ("score", C.c_int32)]
+
+
+FIT_LEAST_ALLOCATED, FIT_MOST_ALLOCATED, FIT_REQUESTED_TO_CAPACITY_RATIO = 0, 1, 2
+FIT_TYPES = {"LeastAllocated": FIT_LEAST_ALLOCATED, "MostAllocated": FIT_MOST_ALLOCATED,
+             "RequestedToCapacityRatio": FIT_REQUESTED_TO_CAPACITY_RATIO}
+FIT_SHAPE_MAX_POINTS = 101
 
 STRUCTS = {
     "ks_label": KsLabel, "ks_taint": KsTaint, "ks_toleration": KsToleration, "ks_node": KsNode,
@@ -336,7 +342,7 @@ KSCHED_SYMBOLS = [
     "ks_comm_init", "ks_comm_allreduce_max", "ks_get_stats", "ks_reset_stats", "ks_set_timing",
     "ks_debug_counters", "ks_debug_set_profile", "ks_debug_resolve_profile", "ks_debug_round_record", "ks_set_sync_timeout", "ks_debug_stall", "ks_batch_marks",
     "ks_debug_runs_started", "ks_next_start_index", "ks_debug_sweep_geometry",
-    "ks_set_fit_strategy", "ks_get_fit_strategy",
+    "ks_set_fit_strategy", "ks_get_fit_strategy", "ks_set_fit_strategy_shape", "ks_get_fit_shape", "ks_fit_shape_table",
 ]
 KSGATHER_SYMBOLS = [
     "ksg_open", "ksg_close", "ksg_set_members", "ksg_record_and_wait", "ksg_pending", "ksg_fnv1_32", "ksg_target_index",
@@ -411,6 +417,9 @@ def ksched_lib() -> C.CDLL:
     L.ks_set_timing.argtypes = [vp, C.c_int32]
     L.ks_set_fit_strategy.argtypes = [vp, P(KsFitStrategy)]
     L.ks_get_fit_strategy.argtypes = [vp, P(KsFitStrategy)]
+    L.ks_set_fit_strategy_shape.argtypes = [vp, P(KsFitStrategy), P(KsFitShapePoint), C.c_uint32]
+    L.ks_get_fit_shape.argtypes = [vp, P(KsFitShapePoint), C.c_uint32, P(C.c_uint32)]
+    L.ks_fit_shape_table.argtypes = [P(KsFitShapePoint), C.c_uint32, P(C.c_uint8)]
     L.ks_debug_counters.argtypes = [vp, P(C.c_uint64)]
     L.ks_debug_sweep_geometry.argtypes = [vp, C.c_int32, P(C.c_uint64)]
     L.ks_debug_set_profile.argtypes = [vp, C.c_int32]

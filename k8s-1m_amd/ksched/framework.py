@@ -119,13 +119,13 @@ class Scheduler:
                  nodes_per_lane: int = 4, world_size: int = 1, rank: int = 0, virtual_shards: int = 1,
                  weights: Optional[Dict[str, int]] = None, options: Optional[Dict[str, int]] = None,
                  percentage_of_nodes_to_score: int = 100, fit_strategy: str = "LeastAllocated",
-                 fit_resource_weights: Optional[Dict[str, int]] = None):
+                 fit_resource_weights: Optional[Dict[str, int]] = None, fit_shape=None):
         """options: ks_config execution options by field name (_abi.OPTION_FIELDS),
         e.g. {"resolve_mode": _abi.RESOLVE_SERIAL, "dedup_identical_pods": 0};
         none of them changes a result.  percentage_of_nodes_to_score: the
         profile's percentageOfNodesToScore (ksched.h; below 100 one shard only).
-        fit_strategy / fit_resource_weights: NodeResourcesFitArgs.scoringStrategy
-        (set_fit_strategy)."""
+        fit_strategy / fit_resource_weights / fit_shape:
+        NodeResourcesFitArgs.scoringStrategy (set_fit_strategy)."""
         self.lib = _abi.ksched_lib()
         cfg = _abi.KsConfig()
         self.lib.ks_config_default(C.byref(cfg))
@@ -160,18 +160,23 @@ class Scheduler:
         self.names: Dict[int, str] = {}
         self.slots: Dict[str, int] = {}
         self.slot_gen: Dict[int, int] = {}  # last NodeInfo.Generation applied per slot (snapshot_update)
-        if fit_strategy != "LeastAllocated" or fit_resource_weights is not None:
+        if fit_strategy != "LeastAllocated" or fit_resource_weights is not None or fit_shape is not None:
             try:
-                self.set_fit_strategy(fit_strategy, fit_resource_weights)
+                self.set_fit_strategy(fit_strategy, fit_resource_weights, fit_shape)
             except Exception:
                 self.close()
                 raise
 
-    def set_fit_strategy(self, strategy: str = "LeastAllocated", resource_weights: Optional[Dict[str, int]] = None):
-        """NodeResourcesFitArgs.scoringStrategy: type "LeastAllocated" or
-        "MostAllocated", resources {"cpu": w, "memory": w} (1..100 each; a
-        resource left out is not scored; default both 1).  Applies to every
-        batch run after the call (ks_set_fit_strategy)."""
+    def set_fit_strategy(self, strategy: str = "LeastAllocated", resource_weights: Optional[Dict[str, int]] = None,
+                         shape=None):
+        """NodeResourcesFitArgs.scoringStrategy: type "LeastAllocated",
+        "MostAllocated" or "RequestedToCapacityRatio", resources {"cpu": w,
+        "memory": w} (1..100 each; a resource left out is not scored; default
+        both 1).  RequestedToCapacityRatio takes shape, a sequence of
+        (utilization 0..100, score 0..10) with strictly increasing
+        utilizations, e.g. [(0, 0), (100, 10)] for bin packing; the other two
+        take none.  Applies to every batch run after the call
+        (ks_set_fit_strategy / ks_set_fit_strategy_shape)."""
         if strategy not in _abi.FIT_TYPES:
             raise ValueError(f"unknown NodeResourcesFit scoring strategy {strategy}")
         w = {"cpu": 1, "memory": 1} if resource_weights is None else dict(resource_weights)
@@ -179,7 +184,21 @@ class Scheduler:
         if unknown:
             raise ValueError(f"NodeResourcesFit scores cpu and memory only, not {sorted(unknown)}")
         fs = _abi.KsFitStrategy(_abi.FIT_TYPES[strategy], int(w.get("cpu", 0)), int(w.get("memory", 0)), 0)
-        self._ok(self.lib.ks_set_fit_strategy(self.ctx, C.byref(fs)))
+        if shape is None:
+            # (RequestedToCapacityRatio without a shape: KS_ERR_INVALID, the library's answer)
+            self._ok(self.lib.ks_set_fit_strategy(self.ctx, C.byref(fs)))
+            return
+        pts = [(int(u), int(v)) for u, v in shape]
+        arr = (_abi.KsFitShapePoint * max(1, len(pts)))(*[_abi.KsFitShapePoint(u, v) for u, v in pts])
+        self._ok(self.lib.ks_set_fit_strategy_shape(self.ctx, C.byref(fs), arr, len(pts)))
+
+    def get_fit_shape(self):
+        """The RequestedToCapacityRatio shape in force as [(utilization, score)];
+        [] under the other two strategies."""
+        arr = (_abi.KsFitShapePoint * _abi.FIT_SHAPE_MAX_POINTS)()
+        n = C.c_uint32()
+        self._ok(self.lib.ks_get_fit_shape(self.ctx, arr, _abi.FIT_SHAPE_MAX_POINTS, C.byref(n)))
+        return [(int(arr[i].utilization), int(arr[i].score)) for i in range(n.value)]
 
     def get_fit_strategy(self):
         """(strategy name, {"cpu": w, "memory": w}) in force."""

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Throughput of the round kernels under a NodeResourcesFit scoring strategy
-(DESIGN §5.9).  bench.py measures the default strategy and has no switch; this
+(DESIGN §5.9, §5.10).  bench.py measures the default strategy and has no switch; this
 tool times the bench's C3 shape -- 1M heterogeneous nodes prefilled below 50 %
 cpu, steps of 50,000 resource-only pods at 256 pods per round -- through the
 ksched Python API under each strategy asked for, and prints one JSON line per
 strategy: pods/s, the parallel commit's passes per round, rounds it handed to
 the serial commit (ks_debug_counters [12]-[15]) and the sweep / resolve time
-per launch.  The figures are reported, not targeted.
+per launch.  The figures are reported, not targeted.  A strategy is
+TYPE:CPU_WEIGHT:MEMORY_WEIGHT; RequestedToCapacityRatio takes its shape as a
+fourth field of UTILIZATION=SCORE points joined by "/".
 
   python3 tools/fit_strategy_rate.py [--strategies LeastAllocated:1:1,MostAllocated:1:1]
+  python3 tools/fit_strategy_rate.py --strategies MostAllocated:1:1,RequestedToCapacityRatio:1:1:0=0/100=10,RequestedToCapacityRatio:1:1:0=0/50=10/100=0
 """
 from __future__ import annotations
 
@@ -33,9 +36,10 @@ def counters(s):
 
 
 def measure(a, nodes, pre, pods, strategy):
-    kind, wc, wm = strategy.split(":")
+    kind, wc, wm, *rest = strategy.split(":")
+    shape = [tuple(int(v) for v in pt.split("=")) for pt in rest[0].split("/")] if rest else None
     with Scheduler(a.nodes, pods_per_round=a.pods_per_round, fit_strategy=kind,
-                   fit_resource_weights={"cpu": int(wc), "memory": int(wm)}) as s:
+                   fit_resource_weights={"cpu": int(wc), "memory": int(wm)}, fit_shape=shape) as s:
         s.upsert_nodes_raw(nodes.nodes, synth.slot_array(a.nodes), a.nodes)
         assert s.lib.ks_pods_add(s.ctx, pre.pods, pre.slot_ptr, pre.n_pods) == 0, s.lib.ks_last_error(s.ctx)
         for k in range(a.warmup):

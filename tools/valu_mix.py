@@ -122,9 +122,9 @@ def pod_loop(ins):
 
 
 def general_variant(mangled: str) -> bool:
-    """sweep_kernel<NPL, EXT, LWU, GF = true>: the instances of a non-default
-    NodeResourcesFit strategy (DESIGN §5.9), which bench.py never runs."""
-    return re.search(r"sweep_kernelILi\d+ELb\dELi\d+ELb1EE", mangled) is not None
+    """sweep_kernel<NPL, EXT, LWU, GF != 0>: the instances of a non-default
+    NodeResourcesFit strategy (DESIGN §5.9, §5.10), which bench.py never runs."""
+    return re.search(r"sweep_kernelILi\d+ELb\dELi\d+ELi[1-9]\d*EE", mangled) is not None
 
 
 def template_args(mangled: str) -> str:
