@@ -678,8 +678,9 @@ ks_status ks_set_timing(ks_ctx *ctx, int32_t enabled);
  * default returns KS_ERR_UNSUPPORTED: the window's only reference is the
  * oracle's own schedule, which knows the default strategy alone, and nothing
  * ships here that a parity test does not pin.
- * Extended resources in the list: not modelled (the struct carries cpu and
- * memory only).
+ * The struct carries cpu and memory; extended resources in the list are set
+ * by ks_set_fit_strategy_resources (below).  ks_set_fit_strategy and
+ * ks_set_fit_strategy_shape CLEAR any extended list in force.
  *
  * RequestedToCapacityRatio (requested_to_capacity_ratio.go, helper/shape_score.go)
  * takes a shape besides the weights: 1..101 points {utilization 0..100, strictly
@@ -701,7 +702,42 @@ ks_status ks_set_timing(ks_ctx *ctx, int32_t enabled);
  * shape (*n points; 0 under the other two types) and returns KS_ERR_INVALID,
  * with *n set, when cap is below it.
  * ks_fit_shape_table needs no context: it validates a shape and fills
- * out[p] = raw(p) for p = 0..100, the table the kernels read. */
+ * out[p] = raw(p) for p = 0..100, the table the kernels read.
+ *
+ * Extended resources in the list (resource_allocation.go#calculateResourceAllocatableRequest):
+ * ks_set_fit_strategy_resources is the superset call.  With n_extended == 0 it
+ * is ks_set_fit_strategy (no shape) or ks_set_fit_strategy_shape (a shape).
+ * With n_extended > 0 it also lists scalar resources {name, weight 1..100}: an
+ * extended vendor/x name, hugepages-*, attachable-volumes-* or a
+ * kubernetes.io/-prefixed native name.  Such a resource is scored only for a
+ * pod whose PodRequests for it is non-zero (for every other pod it adds neither
+ * to the sum nor to the weight sum), with capacity = the node's Allocatable of
+ * it (0: left out, as cpu and memory are) and requested = the node's Requested
+ * -- not NonZeroRequested -- plus the pod's request, the value the fit filter
+ * compares.  The strategies combine it with cpu and memory as above.  weight_cpu
+ * == weight_memory == 0 is valid here (only the extended resources are scored).
+ * The call follows its siblings' rules: it waits for submitted batches, applies
+ * to every batch run afterwards (also one prepared before), ks_plugin_scores
+ * follows it, every rank sets the same strategy.  Listing a name creates no
+ * column: a name no node or pod has shown yet is remembered and takes effect
+ * when its column appears (under the usual KS_NEED_DRAIN rule).
+ * Refusals (none changes the strategy in force):
+ *   KS_ERR_INVALID      a null or empty name; cpu, memory or pods; a repeated
+ *                       name; a name that is neither scalar nor
+ *                       ephemeral-storage; a weight outside 1..100; more than 8
+ *                       names; every invalid input of the sibling calls
+ *   KS_ERR_UNSUPPORTED  ephemeral-storage (upstream scores it for every pod,
+ *                       requesting or not: not modelled); any extended list with
+ *                       percentage_of_nodes_to_score < 100
+ *   KS_ERR_RANGE        a present node's Allocatable of a listed name is >= 2^44
+ *                       (the bound of cpu and memory; unlisted extended
+ *                       resources keep the whole int64 range).  While a name is
+ *                       listed, ks_nodes_upsert / ks_snapshot_update /
+ *                       ks_events_apply refuse such a node the same way, before
+ *                       anything is applied.
+ * ks_get_fit_resources copies the list in force (*n entries, 0 without one;
+ * the names belong to the context and stay valid until the next strategy
+ * call) and returns KS_ERR_INVALID, with *n set, when cap is below it. */
 enum { KS_FIT_LEAST_ALLOCATED = 0, KS_FIT_MOST_ALLOCATED = 1, KS_FIT_REQUESTED_TO_CAPACITY_RATIO = 2 };
 typedef struct {
   int32_t type;           /* KS_FIT_*                       */
@@ -715,6 +751,14 @@ ks_status ks_get_fit_strategy(ks_ctx *ctx, ks_fit_strategy *out);
 ks_status ks_set_fit_strategy_shape(ks_ctx *ctx, const ks_fit_strategy *s, const ks_fit_shape_point *shape, uint32_t n);
 ks_status ks_get_fit_shape(ks_ctx *ctx, ks_fit_shape_point *out, uint32_t cap, uint32_t *n);
 ks_status ks_fit_shape_table(const ks_fit_shape_point *shape, uint32_t n, uint8_t out[101]);
+typedef struct {
+  const char *name;  /* resources: {name, weight} */
+  int32_t weight;    /* 1..100                    */
+  int32_t _pad;
+} ks_fit_resource;
+ks_status ks_set_fit_strategy_resources(ks_ctx *ctx, const ks_fit_strategy *s, const ks_fit_shape_point *shape,
+                                        uint32_t n_shape, const ks_fit_resource *extended, uint32_t n_extended);
+ks_status ks_get_fit_resources(ks_ctx *ctx, ks_fit_resource *out, uint32_t cap, uint32_t *n);
 
 #ifdef __cplusplus
 }

@@ -184,7 +184,9 @@ struct alignas(16) AffDev {
   int32_t weight;  // AF_SCORE: multiplier of the domain sum; AF_OWN: the column unit
 };
 // NodeResourcesFit for an extended resource (ephemeral-storage or a scalar
-// resource): the pod's request and the resource's column.
+// resource): the pod's request and the resource's column.  The record holds
+// nothing of the scoring strategy: when the strategy lists the resource, its
+// weight is looked up by column at launch (SpreadArgs::xw).
 constexpr int MAX_XRES = 8;
 struct alignas(16) XResDev {
   uint32_t col, _pad;

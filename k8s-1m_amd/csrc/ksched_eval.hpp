@@ -316,6 +316,49 @@ __device__ __forceinline__ int32_t score_fit(const PodDev &p, const NodeRegs &r,
   else return score_fit_nz<GF>(p.nz100_cpu, p.nz100_mem, r, f);
 }
 
+// NodeResourcesFit with listed extended resources, scored
+// only for a pod that requests one, so only by the one-pod chain's filter pass
+// and its score dump.  fit_x_resource adds one listed record of the pod to the
+// node's sums from the two column values the fit check loaded: cap =
+// Allocatable, req = Requested + the pod's request (ksched_fit_shape.hpp).
+template <int GF>
+__device__ __forceinline__ void fit_x_resource(FitXSum &x, uint32_t w, int64_t cap, int64_t req, const FitParams &f,
+                                               const uint8_t *T) {
+  static_assert(GF == 1 || GF == 2, "the default strategy lists no extended resource");
+  if constexpr (GF == 2) {
+    const uint32_t u = min(fit_x_score(true, cap, req), 100u);
+    fit_x_add_rtcr(x, w, cap ? (uint32_t)T[u] : 0u);
+  } else {
+    fit_x_add(x, w, fit_x_score(f.most != 0, cap, req), cap != 0);
+  }
+}
+// The node score: cpu and memory as score_fit_general / score_fit_rtcr compute
+// them, added to the extended resources' sums x.  LeastAllocated /
+// MostAllocated divide by the reciprocal multiply: every listed resource the
+// pod requests has non-zero Allocatable on a node that passed the fit filter,
+// so the divisor is W_x (the pod's listed weights) plus the weights of cpu /
+// memory where present -- xrcp[has_cpu + 2 has_mem], computed per pod by the
+// host.  RequestedToCapacityRatio's divisor depends on which table scores are
+// positive: fit_x_round_div.
+template <int GF>
+__device__ __forceinline__ int32_t score_fit_x(const PodDev &p, const NodeRegs &r, const FitParams &f, FitXSum x,
+                                               const uint32_t *xrcp, const uint8_t *T) {
+  if constexpr (GF == 2) {
+    const uint32_t uc = min(fit_resource(true, r.lf100_cpu, p.nz100_cpu, r.acpu_d, r.inv_cpu), 100u);
+    const uint32_t um = min(fit_resource(true, r.lf100_mem, p.nz100_mem, r.amem_d, r.inv_mem), 100u);
+    fit_x_add_rtcr(x, f.wc, r.inv_cpu != 0.0 ? (uint32_t)T[uc] : 0u);
+    fit_x_add_rtcr(x, f.wm, r.inv_mem != 0.0 ? (uint32_t)T[um] : 0u);
+    return (int32_t)fit_x_round_div(x.n, x.d);
+  } else {
+    const uint32_t sc = fit_resource(f.most, r.lf100_cpu, p.nz100_cpu, r.acpu_d, r.inv_cpu);
+    const uint32_t sm = fit_resource(f.most, r.lf100_mem, p.nz100_mem, r.amem_d, r.inv_mem);
+    const uint32_t n = x.n + wmad(f.wc, sc, wmul(f.wm, sm));  // <= 100,000
+    const bool hc = r.inv_cpu != 0.0, hm = r.inv_mem != 0.0;
+    const uint32_t rcp = hc ? (hm ? xrcp[3] : xrcp[1]) : (hm ? xrcp[2] : xrcp[0]);
+    return (int32_t)fit_x_div(n, rcp);
+  }
+}
+
 // RN(a / b) from y = RN(1 / b): q0 = RN(a y) is within one ulp of a/b, the
 // remainder a - b q0 is exact by FMA, and one correction q0 + r y rounds to the
 // IEEE quotient (Markstein).  Checked against true division over the operand

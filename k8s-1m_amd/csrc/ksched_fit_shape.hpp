@@ -81,4 +81,52 @@ KS_HD inline uint32_t fit_rtcr_node_score(uint32_t tc, uint32_t tm, uint32_t wc,
   return (uint32_t)(((uint64_t)((2u * n + d) << 1) * rcp) >> 32);
 }
 
+// ---- listed extended (scalar) resources -------------------
+// The one-FMA floor's epsilon (ksched_eval.hpp LA_EPS).
+constexpr double FIT_X_EPS = 0x1p-45;
+constexpr int64_t FIT_X_MAX_CAP = 1ll << 44;  // a listed resource's Allocatable stays below it (as cpu / memory)
+
+// One listed scalar resource's score from its int64 columns: cap =
+// Allocatable, req = Requested + the pod's request (Requested, not
+// NonZeroRequested).  most: min(req, cap) * 100 / cap, else
+// max(cap - req, 0) * 100 / cap, int64 truncation.  The clamp is taken in
+// int64 first -- Requested may exceed Allocatable by any amount after
+// ks_pods_add -- so the value converted lies in [0, cap], cap < 2^44, its
+// hundredfold is exact and the floor is fit_resource's: y = RN(1 / cap), one
+// FMA, truncation.  cap == 0 -> 0 (the caller leaves the resource out).
+// Checked by tools/xfit_check.cpp.
+KS_HD inline uint32_t fit_x_score(bool most, int64_t cap, int64_t req) {
+  int64_t m = req < cap ? req : cap;  // min(req, cap)
+  m = m > 0 ? m : 0;
+  const int64_t v = most ? m : cap - m;  // in [0, cap]
+  const double y = cap ? 1.0 / (double)cap : 0.0;
+  const double q = __builtin_fma((double)v * 100.0, y, FIT_X_EPS);
+  return (uint32_t)q;  // 0 <= q < 101
+}
+
+// Sum of weight x score (n) and of the weights that count (d) over the
+// resources of one node: at most 10 resources of weight <= 100 and score <=
+// 100, so n <= 100,000 and d <= 1,000.
+struct FitXSum {
+  uint32_t n, d;
+};
+// LeastAllocated / MostAllocated: the resource counts when its Allocatable is non-zero.
+KS_HD inline void fit_x_add(FitXSum &s, uint32_t w, uint32_t score, bool has_cap) {
+  s.n += fit_mul24(w, score);
+  s.d += has_cap ? w : 0u;
+}
+// RequestedToCapacityRatio: t = T[utilisation], 0 for a zero Allocatable; the
+// resource counts when t is positive.
+KS_HD inline void fit_x_add_rtcr(FitXSum &s, uint32_t w, uint32_t t) {
+  s.n += fit_mul24(w, t);
+  s.d += t ? w : 0u;
+}
+// floor(n / d) by the reciprocal multiply, rcp = fit_weight_rcp(d): exact while
+// n x d < 2^31 (here <= 10^8).  d == 0 has rcp == 0 -> 0.
+KS_HD inline uint32_t fit_x_div(uint32_t n, uint32_t rcp) { return (uint32_t)(((uint64_t)(n << 1) * rcp) >> 32); }
+// math.Round(n / d) = floor((2 n + d) / (2 d)): d varies per node over the
+// subsets of the listed resources, so this one is a 32-bit division (the
+// one-pod chain runs it once per feasible node); 2 n + d <= 201,000.
+KS_HD inline uint32_t fit_x_round_div(uint32_t n, uint32_t d) { return d ? (2u * n + d) / (2u * d) : 0u; }
+
 }  // namespace ks

@@ -332,6 +332,7 @@ struct ks_batch {
   std::vector<uint32_t> set_ids;
   std::vector<uint8_t> spread;
   bool any_spread = false;
+  std::vector<uint8_t> xcols;  // per pod: the extended-resource columns its program requests, as a bit mask
   // replica runs: 1 the run kernel models the pod's program,
   // 2 the pod is identical to the one before it (program, labels)
   std::vector<uint8_t> rep;
@@ -405,6 +406,12 @@ struct ks_ctx {
   FitParams fit_params{0, 1, 1, fit_weight_rcp(1), fit_weight_rcp(1), fit_weight_rcp(2)};
   uint32_t fit_general = 0;  // 1 LeastAllocated / MostAllocated, 2 RequestedToCapacityRatio
   std::vector<ks_fit_shape_point> fit_shape;  // the shape in force under RequestedToCapacityRatio (else empty)
+  // Listed extended resources (ks_set_fit_strategy_resources):
+  // interned name and weight, and the names as ks_get_fit_resources hands them
+  // out.  A name need not have a column yet: the weights are resolved to
+  // columns whenever a chain is launched (fit_xweights).
+  std::vector<std::pair<uint32_t, int32_t>> fit_x;
+  std::vector<std::string> fit_x_names;
   // Execution options from ks_config (ks_open), per context, so one process
   // can open contexts with different settings (tests do).
   bool early_fix = true;
@@ -2433,6 +2440,36 @@ uint32_t solo_passes(const SoloHdr *hd) {
   return f;
 }
 
+// Extended-resource columns a one-pod program requests, as a bit mask.
+uint8_t solo_xcols(const SoloHdr *hd) {
+  const XResDev *xr = reinterpret_cast<const XResDev *>(reinterpret_cast<const SpreadDev *>(hd + 1) + hd->n_spread);
+  uint8_t m = 0;
+  for (uint32_t k = 0; k < hd->n_xres; ++k) m |= (uint8_t)(1u << (xr[k].col & (MAX_XRES - 1)));
+  return m;
+}
+
+// The strategy's weight of every extended-resource column, 8 bits each
+// (SpreadArgs::xw): a listed name without a column has no bits.  Under c->mu.
+uint64_t fit_xweights(const ks_ctx *c) {
+  uint64_t xw = 0;
+  for (auto &nw : c->fit_x) {
+    auto it = c->xres_of.find(nw.first);
+    if (it != c->xres_of.end()) xw |= (uint64_t)(uint32_t)nw.second << (8 * it->second);
+  }
+  return xw;
+}
+
+// A chain launch for a program requesting the columns `xcols`: SPL_XFIT and
+// the pod's reciprocals when the strategy in force lists one of them.
+uint32_t xfit_launch(SpreadArgs *sa, uint8_t xcols) {
+  uint32_t wx = 0;
+  for (uint32_t col = 0; col < (uint32_t)MAX_XRES; ++col)
+    if (xcols >> col & 1u) wx += (uint32_t)(sa->xw >> (8 * col)) & 0xFFu;
+  if (!wx || !sa->fit_general) return 0;
+  for (uint32_t k = 0; k < 4; ++k) sa->xrcp[k] = fit_weight_rcp(wx + (k & 1u ? sa->fs.wc : 0u) + (k & 2u ? sa->fs.wm : 0u));
+  return SPL_XFIT;
+}
+
 // Replica runs: the run kernel models a one-pod program with at
 // most one kubernetes.io/hostname constraint (ScheduleAnyway) and one on
 // another key, and no InterPodAffinity, extended-resource or image records.  The inclusion policies need no check: PreScore's per-node
@@ -3344,7 +3381,7 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
           e1 = get_event(c);
           HIPC(c, hipEventRecord(e0, c->stream));
         }
-        HIPC(c, launch_spread_pod(sa, b->spread[i] & 0x7Fu, c->stream));
+        HIPC(c, launch_spread_pod(sa, (b->spread[i] & 0x7Fu) | xfit_launch(&sa, b->xcols[i]), c->stream));
         if (tm) {
           HIPC(c, hipEventRecord(e1, c->stream));
           c->ev_spread.emplace_back(e0, e1);
@@ -3747,12 +3784,24 @@ ks_status check_node_item(const ks_ctx *c, const ks_node &s, uint32_t slot, std:
   }
   // extended / ephemeral columns are only compared (Fit: request >
   // Allocatable - Requested, exact int64), so any non-negative int64 is
-  // exact; the 2^44 bound is LeastAllocated's (cpu and memory only)
-  for (uint32_t k = 0; k < s.n_extended; ++k)
-    if (s.extended && s.extended[k].value < 0) {
+  // exact; the 2^44 bound is LeastAllocated's: cpu, memory and the extended
+  // resources the strategy in force lists (ks_set_fit_strategy_resources)
+  for (uint32_t k = 0; k < s.n_extended; ++k) {
+    if (!s.extended) break;
+    if (s.extended[k].value < 0) {
       *why = "node " + str(s.name) + " extended allocatable negative";
       return KS_ERR_RANGE;
     }
+    if (s.extended[k].value >= kMaxAlloc && !c->fit_x.empty()) {
+      const int32_t id = c->lookup(s.extended[k].name);
+      for (auto &nw : c->fit_x)
+        if (id >= 0 && nw.first == (uint32_t)id) {
+          *why = "node " + str(s.name) + " allocatable of " + str(s.extended[k].name) +
+                 ", a resource the NodeResourcesFit strategy lists, outside the exact range";
+          return KS_ERR_RANGE;
+        }
+    }
+  }
   return KS_OK;
 }
 
@@ -4410,12 +4459,14 @@ ks_status ks_batch_prepare(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_batch *
   b->class_refs = std::move(refs);
   b->term_refs = std::move(term_refs);
   b->spread.assign(n, 0);
+  b->xcols.assign(n, 0);
   b->any_spread = false;
   b->rep.assign(n, 0);
   for (uint32_t i = 0; i < n; ++i) {
     if (!(dev[i].flags & PF_SOLO)) continue;
     const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + dev[i].solo_off);
     b->spread[i] = (uint8_t)(0x80u | solo_passes(hd));
+    b->xcols[i] = solo_xcols(hd);
     b->any_spread = true;
     if (!replica_program(dev[i], hd)) continue;
     b->rep[i] = 1;
@@ -4526,6 +4577,7 @@ SpreadArgs spread_args(ks_ctx *c) {
     std::lock_guard<std::mutex> g(c->mu);
     sa.t = c->t;
     for (uint32_t k = 0; k < c->topo.size(); ++k) sa.ndom[k] = c->topo[k].ndom;
+    sa.xw = fit_xweights(c);
   }
   sa.pos_slot = c->d_pos_slot;
   sa.slot_pos = c->d_slot_pos;
@@ -4573,7 +4625,7 @@ ks_status spread_plugin_scores(ks_ctx *c, const PodDev &d, const ProgBuf &cl, ks
   sa.dump = d_out;
   sa.no_commit = 1;
   const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + d.solo_off);
-  HIPC(c, launch_spread_pod(sa, solo_passes(hd), c->stream));
+  HIPC(c, launch_spread_pod(sa, solo_passes(hd) | xfit_launch(&sa, solo_xcols(hd)), c->stream));
   if ((st = d2h(c, raw.data(), d_out, raw.size() * 4)) || (st = xfer_sync(c))) return st;
   for (uint32_t i = 0; i < c->cap; ++i) {
     const int32_t *o = &raw[(size_t)i * SPREAD_DUMP_WORDS];
@@ -4879,6 +4931,8 @@ ks_status ks_set_fit_strategy(ks_ctx *c, const ks_fit_strategy *s) {
                             fit_weight_rcp(wc + wm)};
   c->fit_general = general ? 1u : 0u;
   c->fit_shape.clear();
+  c->fit_x.clear();  // cpu and memory only
+  c->fit_x_names.clear();
   return KS_OK;
 }
 
@@ -4909,6 +4963,96 @@ ks_status ks_set_fit_strategy_shape(ks_ctx *c, const ks_fit_strategy *s, const k
   c->fit_params = FitParams{2u, wc, wm, fit_weight_rcp(2 * wc), fit_weight_rcp(2 * wm), fit_weight_rcp(2 * (wc + wm))};
   c->fit_general = 2u;
   c->fit_shape.assign(shape, shape + n);
+  c->fit_x.clear();  // cpu and memory only
+  c->fit_x_names.clear();
+  return KS_OK;
+}
+
+ks_status ks_set_fit_strategy_resources(ks_ctx *c, const ks_fit_strategy *s, const ks_fit_shape_point *shape,
+                                        uint32_t n_shape, const ks_fit_resource *extended, uint32_t n_extended) {
+  if (!c || !s) return KS_ERR_INVALID;
+  if (!n_extended) return shape || n_shape ? ks_set_fit_strategy_shape(c, s, shape, n_shape) : ks_set_fit_strategy(c, s);
+  if (!extended) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  const bool rtcr = s->type == KS_FIT_REQUESTED_TO_CAPACITY_RATIO;
+  if (!rtcr && s->type != KS_FIT_LEAST_ALLOCATED && s->type != KS_FIT_MOST_ALLOCATED) return KS_ERR_INVALID;
+  // cpu and memory may both be left out: the extended resources are scored
+  if (s->weight_cpu < 0 || s->weight_cpu > 100 || s->weight_memory < 0 || s->weight_memory > 100) return KS_ERR_INVALID;
+  uint8_t tab[FIT_TABLE_WORDS * 4];
+  if (rtcr) {
+    if (!fit_shape_table(shape, n_shape, tab)) return KS_ERR_INVALID;
+    for (uint32_t i = FIT_TABLE_N; i < sizeof tab; ++i) tab[i] = tab[FIT_TABLE_N - 1];
+  } else if (shape || n_shape) {
+    return KS_ERR_INVALID;
+  }
+  if (n_extended > (uint32_t)MAX_XRES)
+    return c->fail(KS_ERR_INVALID, "more than %d extended resources in the strategy", MAX_XRES);
+  bool ephemeral = false;
+  std::vector<std::string> names;
+  for (uint32_t i = 0; i < n_extended; ++i) {
+    const std::string nm = str(extended[i].name);
+    if (nm.empty() || nm == "cpu" || nm == "memory" || nm == "pods" || !xres_name_ok(nm) ||
+        std::find(names.begin(), names.end(), nm) != names.end())
+      return c->fail(KS_ERR_INVALID, "strategy resource %u: name '%s' (empty, cpu / memory / pods, repeated or not a scalar resource)",
+                     i, nm.c_str());
+    if (extended[i].weight < 1 || extended[i].weight > 100)
+      return c->fail(KS_ERR_INVALID, "strategy resource %s: weight %d outside 1..100", nm.c_str(), extended[i].weight);
+    ephemeral |= nm == "ephemeral-storage";
+    names.push_back(nm);
+  }
+  // upstream scores ephemeral-storage for every pod, requesting or not: a
+  // column of the round kernels, which is not modelled
+  if (ephemeral) return c->fail(KS_ERR_UNSUPPORTED, "ephemeral-storage in the strategy's resources");
+  // as ks_set_fit_strategy: no reference for the window under another strategy
+  if (c->pct != 100) return KS_ERR_UNSUPPORTED;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  ks_status st;
+  // the one-FMA floor's bound on every present node's Allocatable of a listed
+  // name (empty positions hold 0)
+  std::vector<int64_t> colv;
+  for (const std::string &nm : names) {
+    const int32_t id = c->lookup(nm.c_str());
+    uint32_t col = UINT32_MAX;
+    {
+      std::lock_guard<std::mutex> g(c->mu);
+      auto it = id < 0 ? c->xres_of.end() : c->xres_of.find((uint32_t)id);
+      if (it != c->xres_of.end()) col = it->second;
+    }
+    if (col == UINT32_MAX) continue;
+    colv.resize(c->npos);
+    const size_t bytes = (size_t)c->npos * 8;
+    if ((st = xfer_begin(c, 1024, bytes + 1024)) || (st = d2h(c, colv.data(), c->d_xalloc + (size_t)col * c->npos, bytes)) ||
+        (st = xfer_sync(c)))
+      return st;
+    for (int64_t v : colv)
+      if (v >= kMaxAlloc)
+        return c->fail(KS_ERR_RANGE, "a node's allocatable of %s outside the exact range", nm.c_str());
+  }
+  // no batch runs (drained above): the device copy has no reader
+  if (rtcr && ((st = xfer_begin(c, 1024, 0)) || (st = h2d(c, c->d_fit_table, tab, sizeof tab)) || (st = xfer_sync(c))))
+    return st;
+  std::lock_guard<std::mutex> g(c->mu);
+  c->fit = ks_fit_strategy{s->type, s->weight_cpu, s->weight_memory, 0};
+  const uint32_t wc = (uint32_t)s->weight_cpu, wm = (uint32_t)s->weight_memory, m = rtcr ? 2u : 1u;
+  c->fit_params = FitParams{rtcr ? 2u : s->type == KS_FIT_MOST_ALLOCATED ? 1u : 0u, wc, wm, fit_weight_rcp(m * wc),
+                            fit_weight_rcp(m * wm), fit_weight_rcp(m * (wc + wm))};
+  // an extended list makes the strategy general even over {LeastAllocated, 1, 1}
+  c->fit_general = m;
+  if (rtcr) c->fit_shape.assign(shape, shape + n_shape);
+  else c->fit_shape.clear();
+  c->fit_x.clear();
+  for (uint32_t i = 0; i < n_extended; ++i) c->fit_x.emplace_back(c->intern(names[i].c_str()), extended[i].weight);
+  c->fit_x_names = std::move(names);
+  return KS_OK;
+}
+
+ks_status ks_get_fit_resources(ks_ctx *c, ks_fit_resource *out, uint32_t cap, uint32_t *n) {
+  if (!c || !n || (!out && cap)) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  std::lock_guard<std::mutex> g(c->mu);
+  *n = (uint32_t)c->fit_x.size();  // 0: the strategy in force lists cpu and memory only
+  if (cap < *n) return KS_ERR_INVALID;
+  for (uint32_t i = 0; i < *n; ++i) out[i] = ks_fit_resource{c->fit_x_names[i].c_str(), c->fit_x[i].second, 0};
   return KS_OK;
 }
 

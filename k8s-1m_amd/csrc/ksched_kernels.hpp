@@ -121,7 +121,13 @@ constexpr uint32_t SLOT_NONE = 0xFFFFFFFFu;  // position holding no slot (shard 
 constexpr int SPREAD_DUMP_WORDS = 14;
 // launch_spread_pod passes: prep (PodTopologySpread DoNotSchedule counts,
 // InterPodAffinity domain counts), min (criticalPaths), score (ScheduleAnyway)
-enum SpreadLaunch : uint32_t { SPL_PREP = 1u, SPL_MIN = 2u, SPL_SCORE = 4u, SPL_AFF = 8u /* InterPodAffinity records */ };
+enum SpreadLaunch : uint32_t {
+  SPL_PREP = 1u,
+  SPL_MIN = 2u,
+  SPL_SCORE = 4u,
+  SPL_AFF = 8u,    // InterPodAffinity records
+  SPL_XFIT = 16u,  // the strategy in force lists an extended resource the pod requests (decided at launch)
+};
 struct SpreadArgs {
   NodeTable t;
   const uint32_t *pos_slot;   // position -> slot (SLOT_NONE: padding)
@@ -165,7 +171,14 @@ struct SpreadArgs {
   uint32_t nslots;
   uint32_t win_mode;
   int32_t pct;
-  const uint32_t *fit_table;  // as RoundArgs::fit_table
+  // SPL_XFIT: the strategy's weight of each extended-resource
+  // column, 8 bits each (0: not listed), resolved when the chain is launched,
+  // so a program compiled under one strategy scores under the run's; and the
+  // pod's LeastAllocated / MostAllocated reciprocals fit_weight_rcp(W_x +
+  // [cpu present] wc + [memory present] wm) at [has_cpu + 2 has_mem]
+  uint64_t xw;
+  uint32_t xrcp[4];
+  const uint32_t *fit_table;  // as RoundArgs::fit_table (last: the replica kernels load it with ReplicaArgs' head)
 };
 constexpr uint32_t WIN_WORDS = 4;
 

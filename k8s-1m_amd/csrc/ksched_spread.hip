@@ -66,6 +66,16 @@ __device__ __forceinline__ const ImageDev *image_recs(const SpreadArgs &a, const
 __device__ __forceinline__ const AffDev *aff_recs(const SpreadArgs &a, const PodDev &p) {
   return reinterpret_cast<const AffDev *>(image_recs(a, p) + solo_hdr(a, p).n_img);
 }
+// SPL_XFIT: the strategy's weight of an extended-resource column (0: not listed)
+__device__ __forceinline__ uint32_t xfit_weight(const SpreadArgs &a, uint32_t col) {
+  return (uint32_t)(a.xw >> (8u * (col & (MAX_XRES - 1)))) & 0xFFu;
+}
+// RequestedToCapacityRatio's staged shape table (null under the other strategies, which read none)
+template <int GF>
+__device__ __forceinline__ const uint8_t *fit_table_bytes() {
+  if constexpr (GF == 2) return (const uint8_t *)fit_table_lds();
+  else return nullptr;
+}
 // Count column of an InterPodAffinity record at a position.
 __device__ __forceinline__ uint32_t aff_count(const SpreadArgs &a, const AffDev &r, uint32_t pos) {
   return ((r.kind & AF_TERM) ? a.tcnt : a.cnt)[(size_t)r.col * a.npos + pos];
@@ -531,7 +541,9 @@ constexpr int RF = NFILT + 2, R_FEAS = RF, R_IGN = RF + 1, R_TT = RF + 2, R_NA =
 // chain only; as a template parameter the score work compiles away there
 // GF: NodeResourcesFit scored under the context's strategy (a.fs, score_fit;
 // 1 LeastAllocated / MostAllocated with weights, 2 RequestedToCapacityRatio)
-template <bool AFF, bool PROBE = false, int GF = 0>
+// XF: the strategy lists an extended resource the pod requests (SPL_XFIT):
+// the fit check's column values also go into the score (score_fit_x)
+template <bool AFF, bool PROBE = false, int GF = 0, bool XF = false>
 __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a) {
   __shared__ uint32_t s_seen[SP_LDS / 32];
   __shared__ uint32_t s_h[SP_LDS];
@@ -669,12 +681,22 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
       continue;
     }
     int s = filter<true>(p, a.clauses, r, e);
+    FitXSum fx{0, 0};
     if (s == ST_FEASIBLE) {
       // NodeResourcesFit (fitsRequest) for ephemeral-storage / scalar resources
       const XResDev *xr = s_solo.xr;
       for (uint32_t k = 0; k < n_xres; ++k) {
         const size_t ix = (size_t)xr[k].col * a.npos + pos;
-        if (xr[k].req > a.xalloc[ix] - a.xreq[ix]) s = 4;  // KS_PLUGIN_NODE_RESOURCES_FIT
+        if constexpr (XF) {
+          static_assert(GF != 0 && !PROBE, "listed extended resources: a general strategy's score pass");
+          const int64_t xa = a.xalloc[ix], xq = a.xreq[ix];
+          if (xr[k].req > xa - xq) s = 4;
+          // the listed ones into the score (a node failing here is not scored)
+          const uint32_t w = xfit_weight(a, xr[k].col);
+          if (w) fit_x_resource<GF>(fx, w, xa, (int64_t)((uint64_t)xq + (uint64_t)xr[k].req), a.fs, fit_table_bytes<GF>());
+        } else {
+          if (xr[k].req > a.xalloc[ix] - a.xreq[ix]) s = 4;  // KS_PLUGIN_NODE_RESOURCES_FIT
+        }
       }
     }
     if (s == ST_FEASIBLE) {
@@ -706,7 +728,10 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
       const uint32_t nr = (p.flags & PF_NA) ? (uint32_t)preferred_raw(p, a.clauses, e, slot) : 0u;
       tt_max = max(tt_max, tr);
       na_max = max(na_max, nr);
-      a.part[pos] = pack_part((uint32_t)a.w.fit * (uint32_t)score_fit<GF>(p, r, a.fs) + (uint32_t)a.w.ba * (uint32_t)score_ba(p, r) +
+      int32_t fit;
+      if constexpr (XF) fit = score_fit_x<GF>(p, r, a.fs, fx, a.xrcp, fit_table_bytes<GF>());
+      else fit = score_fit<GF>(p, r, a.fs);
+      a.part[pos] = pack_part((uint32_t)a.w.fit * (uint32_t)fit + (uint32_t)a.w.ba * (uint32_t)score_ba(p, r) +
                                   (uint32_t)a.w.il * (uint32_t)image_score(s_solo, e),
                               tr, nr);
       if (ipa_score) {
@@ -1052,7 +1077,9 @@ __global__ __launch_bounds__(WIN_THREADS) void spread_window_kernel(SpreadArgs a
 // pass).
 // RT: the dump under RequestedToCapacityRatio, which reads the shape table's
 // device copy (an instance of its own: the scheduling path's stays as it was)
-template <bool RT = false>
+// XG: the dump under a strategy (1, 2 as GF) that lists an extended resource
+// the pod requests: it reads the pod's records and their columns again
+template <bool RT = false, int XG = 0>
 __global__ __launch_bounds__(SP_THREADS) void spread_select_kernel(SpreadArgs a) {
   __shared__ uint64_t s_r[SP_THREADS / WAVE];
   __shared__ SoloLds s_solo;
@@ -1101,7 +1128,18 @@ __global__ __launch_bounds__(SP_THREADS) void spread_select_kernel(SpreadArgs a)
       load_ext(a.t, pos, true, e);
       int32_t *o = a.dump + (size_t)slot * SPREAD_DUMP_WORDS;
       o[0] = ST_FEASIBLE;
-      if constexpr (RT) o[1] = score_fit_rtcr(p.nz100_cpu, p.nz100_mem, r, a.fs, (const uint8_t *)a.fit_table);
+      if constexpr (XG != 0) {
+        FitXSum fx{0, 0};
+        const XResDev *xr = s_solo.xr;
+        for (uint32_t k = 0; k < s_solo.h.n_xres; ++k) {
+          const size_t ix = (size_t)xr[k].col * a.npos + pos;
+          const uint32_t w = xfit_weight(a, xr[k].col);
+          if (w)
+            fit_x_resource<XG>(fx, w, a.xalloc[ix], (int64_t)((uint64_t)a.xreq[ix] + (uint64_t)xr[k].req), a.fs,
+                               (const uint8_t *)a.fit_table);
+        }
+        o[1] = score_fit_x<XG>(p, r, a.fs, fx, a.xrcp, (const uint8_t *)a.fit_table);
+      } else if constexpr (RT) o[1] = score_fit_rtcr(p.nz100_cpu, p.nz100_mem, r, a.fs, (const uint8_t *)a.fit_table);
       else o[1] = a.fit_general ? score_fit<true>(p, r, a.fs) : score_fit<false>(p, r, a.fs);
       o[2] = score_ba(p, r);
       const int64_t tr = (p.flags & PF_TT) ? taint_raw(p, e) : 0;
@@ -1990,7 +2028,16 @@ hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_
     spread_wcount_kernel<<<(a.nslots + WIN_CHUNK - 1) / WIN_CHUNK, WIN_CHUNK / 16, 0, st>>>(a);
     spread_window_kernel<<<1, WIN_THREADS, 0, st>>>(a);
   }
-  if (a.fit_general == 2) {
+  // SPL_XFIT: a listed extended resource in the pod's records (never with the
+  // default strategy or a window: the setter refuses both)
+  const bool xf = (passes & SPL_XFIT) && a.fit_general && !a.win_mode;
+  if (xf) {
+    if (a.fit_general == 2) {
+      if (passes & SPL_AFF) spread_filter_kernel<true, false, 2, true><<<blocks, SP_THREADS, 0, st>>>(a);
+      else spread_filter_kernel<false, false, 2, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    } else if (passes & SPL_AFF) spread_filter_kernel<true, false, 1, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_filter_kernel<false, false, 1, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  } else if (a.fit_general == 2) {
     if (passes & SPL_AFF) spread_filter_kernel<true, false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
     else spread_filter_kernel<false, false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
   } else if (a.fit_general) {
@@ -1999,7 +2046,10 @@ hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_
   } else if (passes & SPL_AFF) spread_filter_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
   else spread_filter_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
   if (passes & SPL_SCORE) spread_score_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
-  if (a.fit_general == 2 && a.dump) spread_select_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
+  if (xf && a.dump) {
+    if (a.fit_general == 2) spread_select_kernel<false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_select_kernel<false, 1><<<blocks, SP_THREADS, 0, st>>>(a);
+  } else if (a.fit_general == 2 && a.dump) spread_select_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
   else spread_select_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
   spread_commit_kernel<<<1, WAVE, 0, st>>>(a);
   return hipGetLastError();

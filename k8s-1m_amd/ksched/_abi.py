@@ -320,6 +320,11 @@ class KsFitShapePoint(C.Structure):  # ks_fit_shape_point (ks_set_fit_strategy_s
     _fields_ = [("utilization", C.c_int32), ("score", C.c_int32)]
 
 
+class KsFitResource(C.Structure):  # ks_fit_resource (ks_set_fit_strategy_resources / ks_get_fit_resources)
+    _fields_ = [("name", C.c_char_p), ("weight", C.c_int32), ("_pad", C.c_int32)]
+
+
+FIT_MAX_RESOURCES = 8  # extended resources a strategy may list
 FIT_LEAST_ALLOCATED, FIT_MOST_ALLOCATED, FIT_REQUESTED_TO_CAPACITY_RATIO = 0, 1, 2
 FIT_TYPES = {"LeastAllocated": FIT_LEAST_ALLOCATED, "MostAllocated": FIT_MOST_ALLOCATED,
              "RequestedToCapacityRatio": FIT_REQUESTED_TO_CAPACITY_RATIO}
@@ -343,6 +348,7 @@ KSCHED_SYMBOLS = [
     "ks_debug_counters", "ks_debug_set_profile", "ks_debug_resolve_profile", "ks_debug_round_record", "ks_set_sync_timeout", "ks_debug_stall", "ks_batch_marks",
     "ks_debug_runs_started", "ks_next_start_index", "ks_debug_sweep_geometry",
     "ks_set_fit_strategy", "ks_get_fit_strategy", "ks_set_fit_strategy_shape", "ks_get_fit_shape", "ks_fit_shape_table",
+    "ks_set_fit_strategy_resources", "ks_get_fit_resources",
 ]
 KSGATHER_SYMBOLS = [
     "ksg_open", "ksg_close", "ksg_set_members", "ksg_record_and_wait", "ksg_pending", "ksg_fnv1_32", "ksg_target_index",
@@ -420,6 +426,9 @@ def ksched_lib() -> C.CDLL:
     L.ks_set_fit_strategy_shape.argtypes = [vp, P(KsFitStrategy), P(KsFitShapePoint), C.c_uint32]
     L.ks_get_fit_shape.argtypes = [vp, P(KsFitShapePoint), C.c_uint32, P(C.c_uint32)]
     L.ks_fit_shape_table.argtypes = [P(KsFitShapePoint), C.c_uint32, P(C.c_uint8)]
+    L.ks_set_fit_strategy_resources.argtypes = [vp, P(KsFitStrategy), P(KsFitShapePoint), C.c_uint32, P(KsFitResource),
+                                                C.c_uint32]
+    L.ks_get_fit_resources.argtypes = [vp, P(KsFitResource), C.c_uint32, P(C.c_uint32)]
     L.ks_debug_counters.argtypes = [vp, P(C.c_uint64)]
     L.ks_debug_sweep_geometry.argtypes = [vp, C.c_int32, P(C.c_uint64)]
     L.ks_debug_set_profile.argtypes = [vp, C.c_int32]

@@ -172,7 +172,9 @@ class Scheduler:
         """NodeResourcesFitArgs.scoringStrategy: type "LeastAllocated",
         "MostAllocated" or "RequestedToCapacityRatio", resources {"cpu": w,
         "memory": w} (1..100 each; a resource left out is not scored; default
-        both 1).  RequestedToCapacityRatio takes shape, a sequence of
+        both 1); further names are scalar resources, {"amd.com/gpu": 3}, scored
+        for the pods that request them (ks_set_fit_strategy_resources, which
+        judges the names).  RequestedToCapacityRatio takes shape, a sequence of
         (utilization 0..100, score 0..10) with strictly increasing
         utilizations, e.g. [(0, 0), (100, 10)] for bin packing; the other two
         take none.  Applies to every batch run after the call
@@ -180,10 +182,15 @@ class Scheduler:
         if strategy not in _abi.FIT_TYPES:
             raise ValueError(f"unknown NodeResourcesFit scoring strategy {strategy}")
         w = {"cpu": 1, "memory": 1} if resource_weights is None else dict(resource_weights)
-        unknown = set(w) - {"cpu", "memory"}
-        if unknown:
-            raise ValueError(f"NodeResourcesFit scores cpu and memory only, not {sorted(unknown)}")
         fs = _abi.KsFitStrategy(_abi.FIT_TYPES[strategy], int(w.get("cpu", 0)), int(w.get("memory", 0)), 0)
+        ext = [(str(k), int(v)) for k, v in w.items() if k not in ("cpu", "memory")]
+        if ext:  # scalar resources in the list: the library judges the names
+            pts = [] if shape is None else [(int(u), int(v)) for u, v in shape]
+            arr = (_abi.KsFitShapePoint * max(1, len(pts)))(*[_abi.KsFitShapePoint(u, v) for u, v in pts])
+            res = (_abi.KsFitResource * len(ext))(*[_abi.KsFitResource(k.encode(), v, 0) for k, v in ext])
+            self._ok(self.lib.ks_set_fit_strategy_resources(self.ctx, C.byref(fs), None if shape is None else arr,
+                                                            len(pts), res, len(ext)))
+            return
         if shape is None:
             # (RequestedToCapacityRatio without a shape: KS_ERR_INVALID, the library's answer)
             self._ok(self.lib.ks_set_fit_strategy(self.ctx, C.byref(fs)))
@@ -201,11 +208,18 @@ class Scheduler:
         return [(int(arr[i].utilization), int(arr[i].score)) for i in range(n.value)]
 
     def get_fit_strategy(self):
-        """(strategy name, {"cpu": w, "memory": w}) in force."""
+        """(strategy name, {"cpu": w, "memory": w}) in force; the dict also
+        carries the extended resources when the strategy lists any."""
         fs = _abi.KsFitStrategy()
         self._ok(self.lib.ks_get_fit_strategy(self.ctx, C.byref(fs)))
         name = next(k for k, v in _abi.FIT_TYPES.items() if v == fs.type)
-        return name, {"cpu": int(fs.weight_cpu), "memory": int(fs.weight_memory)}
+        w = {"cpu": int(fs.weight_cpu), "memory": int(fs.weight_memory)}
+        res = (_abi.KsFitResource * _abi.FIT_MAX_RESOURCES)()
+        n = C.c_uint32()
+        self._ok(self.lib.ks_get_fit_resources(self.ctx, res, _abi.FIT_MAX_RESOURCES, C.byref(n)))
+        for i in range(n.value):
+            w[res[i].name.decode()] = int(res[i].weight)
+        return name, w
 
     def next_start_index(self) -> int:
         """Scheduler.nextStartNodeIndex (percentageOfNodesToScore < 100)."""
