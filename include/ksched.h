@@ -760,6 +760,47 @@ ks_status ks_set_fit_strategy_resources(ks_ctx *ctx, const ks_fit_strategy *s, c
                                         uint32_t n_shape, const ks_fit_resource *extended, uint32_t n_extended);
 ks_status ks_get_fit_resources(ks_ctx *ctx, ks_fit_resource *out, uint32_t cap, uint32_t *n);
 
+/* NodeResourcesBalancedAllocationArgs.resources (upstream v1.31.3
+ * noderesources/balanced_allocation.go#balancedResourceScorer; DESIGN.md
+ * §5.12).  names: the ordered list; upstream accepts weights there and this
+ * scorer does not read them, so the call takes none.  Per node the list is
+ * walked in order: cpu and memory give Allocatable and Requested + the pod's
+ * request; a scalar resource (an extended vendor/x name, hugepages-*,
+ * attachable-volumes-*, a kubernetes.io/-prefixed native name) is bypassed
+ * for a pod whose PodRequests for it is 0 and otherwise gives the node's
+ * Allocatable and Requested + the request of it.  A zero Allocatable leaves
+ * the resource out; fraction = min(requested / allocatable, 1) in float64.
+ * Zero or one fraction: std = 0; two: |f0 - f1| / 2; more: the square root of
+ * the fractions' variance, mean and squares summed in list order -- the order
+ * of the names is the float64 summation order and can change a score.  Score
+ * = int64((1 - std) * 100), bit for bit upstream's on amd64.
+ * Only a pod that requests a listed scalar resource scores differently from
+ * the default list, and such a pod takes the one-pod chain.  The call follows
+ * the ks_set_fit_strategy* rules: it waits for submitted batches, applies to
+ * every batch run afterwards (also one prepared before), ks_plugin_scores
+ * follows it (balanced_allocation and total_score), every rank sets the same
+ * list.  Listing a name creates no column: a name no node or pod has shown yet
+ * is remembered and takes effect when its column appears.  n == 0 restores
+ * [cpu, memory].
+ * Refusals (none changes the list in force):
+ *   KS_ERR_INVALID      a null or empty name; a repeated name; pods; a name
+ *                       that is neither cpu, memory, scalar nor
+ *                       ephemeral-storage; more than 8 scalar names
+ *   KS_ERR_UNSUPPORTED  ephemeral-storage (upstream scores it for every pod);
+ *                       a list that lacks cpu or memory (it would change every
+ *                       pod's score); any list other than [cpu, memory] with
+ *                       percentage_of_nodes_to_score < 100
+ *   KS_ERR_RANGE        a present node's Allocatable of a listed scalar name is
+ *                       >= 2^44.  While a name is listed, ks_nodes_upsert /
+ *                       ks_snapshot_update / ks_events_apply refuse such a node
+ *                       the same way, before anything is applied.
+ * ks_get_balanced_resources copies the list in force (*n names, [cpu, memory]
+ * by default; they belong to the context and stay valid until the next
+ * ks_set_balanced_resources) and returns KS_ERR_INVALID, with *n set, when cap
+ * is below it. */
+ks_status ks_set_balanced_resources(ks_ctx *ctx, const char *const *names, uint32_t n);
+ks_status ks_get_balanced_resources(ks_ctx *ctx, const char **out, uint32_t cap, uint32_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "ksched.h"
+#include "ksched_ba.hpp"
 #include "ksched_dev.hpp"
 #include "ksched_kernels.hpp"
 #include "ksched_sync.hpp"
@@ -333,6 +334,7 @@ struct ks_batch {
   std::vector<uint8_t> spread;
   bool any_spread = false;
   std::vector<uint8_t> xcols;  // per pod: the extended-resource columns its program requests, as a bit mask
+  std::vector<uint32_t> xrecs;  // per pod: the record (XResDev) of each such column, 4 bits per column
   // replica runs: 1 the run kernel models the pod's program,
   // 2 the pod is identical to the one before it (program, labels)
   std::vector<uint8_t> rep;
@@ -412,6 +414,13 @@ struct ks_ctx {
   // columns whenever a chain is launched (fit_xweights).
   std::vector<std::pair<uint32_t, int32_t>> fit_x;
   std::vector<std::string> fit_x_names;
+  // NodeResourcesBalancedAllocationArgs.resources (ks_set_balanced_resources;
+  // DESIGN.md §5.12), in list order: -1 cpu, -2 memory, else the interned
+  // scalar name; and the names as ks_get_balanced_resources hands them out.
+  // Empty: the default [cpu, memory].  As fit_x, a name need not have a column
+  // yet: the list is resolved whenever a chain is launched (ba_columns).
+  std::vector<int64_t> ba_list;
+  std::vector<std::string> ba_names;
   // Execution options from ks_config (ks_open), per context, so one process
   // can open contexts with different settings (tests do).
   bool early_fix = true;
@@ -2470,6 +2479,52 @@ uint32_t xfit_launch(SpreadArgs *sa, uint8_t xcols) {
   return SPL_XFIT;
 }
 
+// The record of each extended-resource column a one-pod program requests, 4
+// bits per column (with solo_xcols telling which columns are present).
+uint32_t solo_xrecs(const SoloHdr *hd) {
+  const XResDev *xr = reinterpret_cast<const XResDev *>(reinterpret_cast<const SpreadDev *>(hd + 1) + hd->n_spread);
+  uint32_t m = 0;
+  for (uint32_t k = 0; k < hd->n_xres && k < (uint32_t)MAX_XRES; ++k) m |= k << (4 * (xr[k].col & (MAX_XRES - 1)));
+  return m;
+}
+
+// The balanced list in force by column (ksched_ba.hpp's packing with a column
+// for a record): a listed name without a column has no entry.  0: the default.
+uint64_t ba_columns(ks_ctx *c) {
+  std::lock_guard<std::mutex> g(c->mu);
+  uint64_t l = 0;
+  for (int64_t id : c->ba_list) {
+    if (id < 0) {
+      l = ba_list_push(l, id == -1 ? BA_CPU : BA_MEM);
+      continue;
+    }
+    auto it = c->xres_of.find((uint32_t)id);
+    if (it != c->xres_of.end()) l = ba_list_push(l, it->second);
+  }
+  return l;
+}
+
+// A chain launch for a program requesting the columns `xcols` at the records
+// `xrecs`: SPL_BAL and the list as this pod sees it (SpreadArgs::bal_lo / bal_hi) when the
+// balanced list in force names one of them.  Every other pod has cpu and
+// memory alone, in either order: the default scorer's value.
+uint32_t ba_launch(SpreadArgs *sa, uint64_t by_col, uint8_t xcols, uint32_t xrecs) {
+  uint64_t l = 0;
+  bool scalar = false;
+  for (uint32_t j = 0; j < ba_list_count(by_col); ++j) {
+    const uint32_t e = ba_list_entry(by_col, j);
+    if (e >= BA_CPU) {
+      l = ba_list_push(l, e);
+    } else if (xcols >> e & 1u) {
+      l = ba_list_push(l, (xrecs >> (4 * e)) & 0xFu);
+      scalar = true;
+    }
+  }
+  sa->bal_lo = scalar ? (uint32_t)l : 0u;
+  sa->bal_hi = scalar ? (uint32_t)(l >> 32) : 0u;
+  return scalar ? SPL_BAL : 0u;
+}
+
 // Replica runs: the run kernel models a one-pod program with at
 // most one kubernetes.io/hostname constraint (ScheduleAnyway) and one on
 // another key, and no InterPodAffinity, extended-resource or image records.  The inclusion policies need no check: PreScore's per-node
@@ -3359,6 +3414,7 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
     uint32_t hi = lo;
     if (b->any_spread && b->spread[lo]) {
       SpreadArgs sa = spread_args(c);
+      const uint64_t ba_cols = ba_columns(c);
       sa.pods = b->d_pods;
       sa.clauses = b->d_clauses;
       sa.cmask = b->d_cmask;
@@ -3381,7 +3437,9 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
           e1 = get_event(c);
           HIPC(c, hipEventRecord(e0, c->stream));
         }
-        HIPC(c, launch_spread_pod(sa, (b->spread[i] & 0x7Fu) | xfit_launch(&sa, b->xcols[i]), c->stream));
+        HIPC(c, launch_spread_pod(sa, (b->spread[i] & 0x7Fu) | xfit_launch(&sa, b->xcols[i]) |
+                                          ba_launch(&sa, ba_cols, b->xcols[i], b->xrecs[i]),
+                                  c->stream));
         if (tm) {
           HIPC(c, hipEventRecord(e1, c->stream));
           c->ev_spread.emplace_back(e0, e1);
@@ -3798,6 +3856,15 @@ ks_status check_node_item(const ks_ctx *c, const ks_node &s, uint32_t slot, std:
         if (id >= 0 && nw.first == (uint32_t)id) {
           *why = "node " + str(s.name) + " allocatable of " + str(s.extended[k].name) +
                  ", a resource the NodeResourcesFit strategy lists, outside the exact range";
+          return KS_ERR_RANGE;
+        }
+    }
+    if (s.extended[k].value >= kMaxAlloc && !c->ba_list.empty()) {
+      const int32_t id = c->lookup(s.extended[k].name);
+      for (int64_t l : c->ba_list)
+        if (id >= 0 && l == (int64_t)id) {
+          *why = "node " + str(s.name) + " allocatable of " + str(s.extended[k].name) +
+                 ", a resource NodeResourcesBalancedAllocation lists, outside the exact range";
           return KS_ERR_RANGE;
         }
     }
@@ -4460,6 +4527,7 @@ ks_status ks_batch_prepare(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_batch *
   b->term_refs = std::move(term_refs);
   b->spread.assign(n, 0);
   b->xcols.assign(n, 0);
+  b->xrecs.assign(n, 0);
   b->any_spread = false;
   b->rep.assign(n, 0);
   for (uint32_t i = 0; i < n; ++i) {
@@ -4467,6 +4535,7 @@ ks_status ks_batch_prepare(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_batch *
     const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + dev[i].solo_off);
     b->spread[i] = (uint8_t)(0x80u | solo_passes(hd));
     b->xcols[i] = solo_xcols(hd);
+    b->xrecs[i] = solo_xrecs(hd);
     b->any_spread = true;
     if (!replica_program(dev[i], hd)) continue;
     b->rep[i] = 1;
@@ -4625,7 +4694,9 @@ ks_status spread_plugin_scores(ks_ctx *c, const PodDev &d, const ProgBuf &cl, ks
   sa.dump = d_out;
   sa.no_commit = 1;
   const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + d.solo_off);
-  HIPC(c, launch_spread_pod(sa, solo_passes(hd) | xfit_launch(&sa, solo_xcols(hd)), c->stream));
+  HIPC(c, launch_spread_pod(sa, solo_passes(hd) | xfit_launch(&sa, solo_xcols(hd)) |
+                                    ba_launch(&sa, ba_columns(c), solo_xcols(hd), solo_xrecs(hd)),
+                            c->stream));
   if ((st = d2h(c, raw.data(), d_out, raw.size() * 4)) || (st = xfer_sync(c))) return st;
   for (uint32_t i = 0; i < c->cap; ++i) {
     const int32_t *o = &raw[(size_t)i * SPREAD_DUMP_WORDS];
@@ -5043,6 +5114,82 @@ ks_status ks_set_fit_strategy_resources(ks_ctx *c, const ks_fit_strategy *s, con
   c->fit_x.clear();
   for (uint32_t i = 0; i < n_extended; ++i) c->fit_x.emplace_back(c->intern(names[i].c_str()), extended[i].weight);
   c->fit_x_names = std::move(names);
+  return KS_OK;
+}
+
+ks_status ks_set_balanced_resources(ks_ctx *c, const char *const *names, uint32_t n) {
+  if (!c || (n && !names)) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  std::vector<std::string> list;
+  bool ephemeral = false, cpu = false, mem = false;
+  uint32_t scalars = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const std::string nm = str(names[i]);
+    if (nm.empty() || nm == "pods" || (nm != "cpu" && nm != "memory" && !xres_name_ok(nm)) ||
+        std::find(list.begin(), list.end(), nm) != list.end())
+      return c->fail(KS_ERR_INVALID, "balanced resource %u: name '%s' (empty, pods, repeated or not cpu, memory or a scalar resource)",
+                     i, nm.c_str());
+    cpu |= nm == "cpu";
+    mem |= nm == "memory";
+    ephemeral |= nm == "ephemeral-storage";
+    if (nm != "cpu" && nm != "memory" && ++scalars > (uint32_t)MAX_XRES)
+      return c->fail(KS_ERR_INVALID, "more than %d scalar resources in the balanced list", MAX_XRES);
+    list.push_back(nm);
+  }
+  // upstream scores ephemeral-storage for every pod, requesting or not, and a
+  // list without cpu or memory changes every pod's score: both would reach the
+  // round kernels, which are not modelled under a list
+  if (ephemeral) return c->fail(KS_ERR_UNSUPPORTED, "ephemeral-storage in the balanced list");
+  if (n && (!cpu || !mem)) return c->fail(KS_ERR_UNSUPPORTED, "a balanced list without cpu or memory");
+  const bool dflt = !n || (n == 2 && list[0] == "cpu");
+  // as ks_set_fit_strategy: no reference for the window under another list
+  if (!dflt && c->pct != 100) return KS_ERR_UNSUPPORTED;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  ks_status st;
+  // the bound on every present node's Allocatable of a listed name, as
+  // ks_set_fit_strategy_resources checks it
+  std::vector<int64_t> colv;
+  for (const std::string &nm : list) {
+    if (nm == "cpu" || nm == "memory") continue;
+    const int32_t id = c->lookup(nm.c_str());
+    uint32_t col = UINT32_MAX;
+    {
+      std::lock_guard<std::mutex> g(c->mu);
+      auto it = id < 0 ? c->xres_of.end() : c->xres_of.find((uint32_t)id);
+      if (it != c->xres_of.end()) col = it->second;
+    }
+    if (col == UINT32_MAX) continue;
+    colv.resize(c->npos);
+    const size_t bytes = (size_t)c->npos * 8;
+    if ((st = xfer_begin(c, 1024, bytes + 1024)) || (st = d2h(c, colv.data(), c->d_xalloc + (size_t)col * c->npos, bytes)) ||
+        (st = xfer_sync(c)))
+      return st;
+    for (int64_t v : colv)
+      if (v >= kMaxAlloc)
+        return c->fail(KS_ERR_RANGE, "a node's allocatable of %s outside the exact range", nm.c_str());
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  c->ba_list.clear();
+  c->ba_names.clear();
+  if (dflt) return KS_OK;
+  for (const std::string &nm : list)
+    c->ba_list.push_back(nm == "cpu" ? -1 : nm == "memory" ? -2 : (int64_t)c->intern(nm.c_str()));
+  c->ba_names = std::move(list);
+  return KS_OK;
+}
+
+ks_status ks_get_balanced_resources(ks_ctx *c, const char **out, uint32_t cap, uint32_t *n) {
+  if (!c || !n || (!out && cap)) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  std::lock_guard<std::mutex> g(c->mu);
+  *n = c->ba_names.empty() ? 2u : (uint32_t)c->ba_names.size();
+  if (cap < *n) return KS_ERR_INVALID;
+  if (c->ba_names.empty()) {
+    out[0] = "cpu";
+    out[1] = "memory";
+  } else {
+    for (uint32_t i = 0; i < *n; ++i) out[i] = c->ba_names[i].c_str();
+  }
   return KS_OK;
 }
 

@@ -127,6 +127,7 @@ enum SpreadLaunch : uint32_t {
   SPL_SCORE = 4u,
   SPL_AFF = 8u,    // InterPodAffinity records
   SPL_XFIT = 16u,  // the strategy in force lists an extended resource the pod requests (decided at launch)
+  SPL_BAL = 32u,   // the balanced list in force names a scalar resource the pod requests (decided at launch)
 };
 struct SpreadArgs {
   NodeTable t;
@@ -154,6 +155,14 @@ struct SpreadArgs {
   DevResult *results;
   int32_t *dump;              // ks_plugin_scores: [slots][SPREAD_DUMP_WORDS] (null: schedule)
   uint32_t no_commit;         // dump / reset: no result, no AssumePod
+  // SPL_BAL: NodeResourcesBalancedAllocationArgs.resources
+  // as this pod sees it -- the entries that take part, in list order, resolved
+  // to the pod's records when the chain is launched (ksched_ba.hpp), so a
+  // program compiled under one list scores under the run's.  0: score_ba.  Its
+  // two halves fill the struct's two alignment holes (here and after pct), so
+  // no member moves and the size stays: every kernel compiled before reads its
+  // arguments where it did
+  uint32_t bal_lo;
   uint64_t *counters;
   Weights w;
   FitParams fs;               // as RoundArgs::fs / fit_general
@@ -171,6 +180,7 @@ struct SpreadArgs {
   uint32_t nslots;
   uint32_t win_mode;
   int32_t pct;
+  uint32_t bal_hi;            // (bal_lo above)
   // SPL_XFIT: the strategy's weight of each extended-resource
   // column, 8 bits each (0: not listed), resolved when the chain is launched,
   // so a program compiled under one strategy scores under the run's; and the

@@ -33,6 +33,7 @@
 // (zones), with global atomics only for high-cardinality ones (hostnames).
 #include <hip/hip_runtime.h>
 
+#include "ksched_ba.hpp"
 #include "ksched_dev.hpp"
 #include "ksched_eval.hpp"
 #include "ksched_kernels.hpp"
@@ -75,6 +76,52 @@ template <int GF>
 __device__ __forceinline__ const uint8_t *fit_table_bytes() {
   if constexpr (GF == 2) return (const uint8_t *)fit_table_lds();
   else return nullptr;
+}
+// SPL_BAL: NodeResourcesBalancedAllocation over the list in force (a.bal_lo / bal_hi:
+// the entries that take part for this pod, in list order; ksched_ba.hpp).  cpu
+// and memory are score_ba's fractions; a listed scalar resource's come from
+// its two columns at the pod's record, the values the fit check compared.  The
+// list's order is not the records', and ba_score_list asks for every fraction
+// twice; the filter instances have no registers for ten doubles, so the filter
+// pass keeps the fractions of the pod's first BA_KEEP records from its fit
+// check (xf0, xf1; negative: the node's Allocatable is 0) -- one listed
+// resource, the common case, then costs no second load and one reciprocal --
+// and the fractions of further records are computed from a second read of the
+// two columns, once per pass.  The dump (KEPT false) reads them all again.
+constexpr uint32_t BA_KEEP = 2;
+__device__ __forceinline__ uint32_t ba_listed_records(const SpreadArgs &a) {
+  const uint64_t bal = (uint64_t)a.bal_hi << 32 | a.bal_lo;
+  uint32_t m = 0;
+  for (uint32_t j = 0; j < ba_list_count(bal); ++j) m |= 1u << ba_list_entry(bal, j);
+  return m & ((1u << MAX_XRES) - 1u);
+}
+template <bool KEPT>
+__device__ __forceinline__ int32_t score_ba_list(const SpreadArgs &a, const PodDev &p, const NodeRegs &r,
+                                                 const XResDev *xr, uint32_t pos, double xf0 = 0.0, double xf1 = 0.0) {
+  return ba_score_list((uint64_t)a.bal_hi << 32 | a.bal_lo, [&](uint32_t e, double &f) {
+    if (e == BA_CPU) {
+      if (r.inv_cpu == 0.0) return false;
+      f = fmin(div_rn(r.rcpu + p.req_cpu_d, r.acpu_d, r.inv_cpu), 1.0);
+      return true;
+    }
+    if (e == BA_MEM) {
+      if (r.inv_mem == 0.0) return false;
+      f = fmin(div_rn(r.rmem + p.req_mem_d, r.amem_d, r.inv_mem), 1.0);
+      return true;
+    }
+    if constexpr (KEPT) {
+      if (e < BA_KEEP) {
+        f = e ? xf1 : xf0;
+        return f >= 0.0;
+      }
+    }
+    const XResDev &x = xr[e & (MAX_XRES - 1)];
+    const size_t ix = (size_t)(x.col & (MAX_XRES - 1)) * a.npos + pos;
+    const int64_t xa = a.xalloc[ix];
+    if (xa == 0) return false;
+    f = ba_x_fraction(xa, (int64_t)((uint64_t)a.xreq[ix] + (uint64_t)x.req));
+    return true;
+  });
 }
 // Count column of an InterPodAffinity record at a position.
 __device__ __forceinline__ uint32_t aff_count(const SpreadArgs &a, const AffDev &r, uint32_t pos) {
@@ -543,7 +590,9 @@ constexpr int RF = NFILT + 2, R_FEAS = RF, R_IGN = RF + 1, R_TT = RF + 2, R_NA =
 // 1 LeastAllocated / MostAllocated with weights, 2 RequestedToCapacityRatio)
 // XF: the strategy lists an extended resource the pod requests (SPL_XFIT):
 // the fit check's column values also go into the score (score_fit_x)
-template <bool AFF, bool PROBE = false, int GF = 0, bool XF = false>
+// BAL: BalancedAllocation over a list that names a scalar resource the pod
+// requests (SPL_BAL; under every GF and XF): score_ba_list for score_ba
+template <bool AFF, bool PROBE = false, int GF = 0, bool XF = false, bool BAL = false>
 __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a) {
   __shared__ uint32_t s_seen[SP_LDS / 32];
   __shared__ uint32_t s_h[SP_LDS];
@@ -587,6 +636,7 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
     if ((sd[c].flags & (SP_SCORE | SP_HOST)) == SP_SCORE && sd[c].cls != CLS_NONE) want_cnt |= 1u << c;
   __syncthreads();
   const uint32_t n_xres = s_solo.h.n_xres;
+  const uint32_t bal_recs = BAL ? ba_listed_records(a) : 0u;  // the pod's records the balanced list names
   const AffDev *ad = s_solo.ad;
   const uint32_t na = AFF ? s_solo.h.n_aff : 0u;
   bool ipa_filter = false;
@@ -682,12 +732,27 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
     }
     int s = filter<true>(p, a.clauses, r, e);
     FitXSum fx{0, 0};
+    double bxf0 = -1.0, bxf1 = -1.0;  // BAL: the fractions of the pod's first records (score_ba_list)
     if (s == ST_FEASIBLE) {
       // NodeResourcesFit (fitsRequest) for ephemeral-storage / scalar resources
       const XResDev *xr = s_solo.xr;
       for (uint32_t k = 0; k < n_xres; ++k) {
         const size_t ix = (size_t)xr[k].col * a.npos + pos;
-        if constexpr (XF) {
+        if constexpr (BAL) {
+          static_assert(!PROBE, "a balanced list: a score pass");
+          const int64_t xa = a.xalloc[ix], xq = a.xreq[ix];
+          if (xr[k].req > xa - xq) s = 4;
+          const int64_t rq = (int64_t)((uint64_t)xq + (uint64_t)xr[k].req);
+          if constexpr (XF) {
+            const uint32_t w = xfit_weight(a, xr[k].col);
+            if (w) fit_x_resource<GF>(fx, w, xa, rq, a.fs, fit_table_bytes<GF>());
+          }
+          if (k < BA_KEEP && (bal_recs >> k & 1u) && xa != 0) {
+            const double f = ba_x_fraction(xa, rq);
+            if (k) bxf1 = f;
+            else bxf0 = f;
+          }
+        } else if constexpr (XF) {
           static_assert(GF != 0 && !PROBE, "listed extended resources: a general strategy's score pass");
           const int64_t xa = a.xalloc[ix], xq = a.xreq[ix];
           if (xr[k].req > xa - xq) s = 4;
@@ -731,9 +796,15 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
       int32_t fit;
       if constexpr (XF) fit = score_fit_x<GF>(p, r, a.fs, fx, a.xrcp, fit_table_bytes<GF>());
       else fit = score_fit<GF>(p, r, a.fs);
-      a.part[pos] = pack_part((uint32_t)a.w.fit * (uint32_t)fit + (uint32_t)a.w.ba * (uint32_t)score_ba(p, r) +
-                                  (uint32_t)a.w.il * (uint32_t)image_score(s_solo, e),
-                              tr, nr);
+      if constexpr (BAL) {
+        a.part[pos] = pack_part((uint32_t)a.w.fit * (uint32_t)fit +
+                                    (uint32_t)a.w.ba * (uint32_t)score_ba_list<true>(a, p, r, s_solo.xr, pos, bxf0, bxf1) +
+                                    (uint32_t)a.w.il * (uint32_t)image_score(s_solo, e),
+                                tr, nr);
+      } else  // (the statement every instance without a list was compiled from)
+        a.part[pos] = pack_part((uint32_t)a.w.fit * (uint32_t)fit + (uint32_t)a.w.ba * (uint32_t)score_ba(p, r) +
+                                    (uint32_t)a.w.il * (uint32_t)image_score(s_solo, e),
+                                tr, nr);
       if (ipa_score) {
         const int64_t raw = ipa_raw_score(a, ad, na, av, pos);
         a.ipa_raw[pos] = raw;
@@ -1079,7 +1150,9 @@ __global__ __launch_bounds__(WIN_THREADS) void spread_window_kernel(SpreadArgs a
 // device copy (an instance of its own: the scheduling path's stays as it was)
 // XG: the dump under a strategy (1, 2 as GF) that lists an extended resource
 // the pod requests: it reads the pod's records and their columns again
-template <bool RT = false, int XG = 0>
+// BAL: the dump under a balanced list that names a scalar resource the pod
+// requests (as the filter pass's)
+template <bool RT = false, int XG = 0, bool BAL = false>
 __global__ __launch_bounds__(SP_THREADS) void spread_select_kernel(SpreadArgs a) {
   __shared__ uint64_t s_r[SP_THREADS / WAVE];
   __shared__ SoloLds s_solo;
@@ -1141,7 +1214,8 @@ __global__ __launch_bounds__(SP_THREADS) void spread_select_kernel(SpreadArgs a)
         o[1] = score_fit_x<XG>(p, r, a.fs, fx, a.xrcp, (const uint8_t *)a.fit_table);
       } else if constexpr (RT) o[1] = score_fit_rtcr(p.nz100_cpu, p.nz100_mem, r, a.fs, (const uint8_t *)a.fit_table);
       else o[1] = a.fit_general ? score_fit<true>(p, r, a.fs) : score_fit<false>(p, r, a.fs);
-      o[2] = score_ba(p, r);
+      if constexpr (BAL) o[2] = score_ba_list<false>(a, p, r, s_solo.xr, pos);
+      else o[2] = score_ba(p, r);
       const int64_t tr = (p.flags & PF_TT) ? taint_raw(p, e) : 0;
       o[3] = (int32_t)tr;
       o[4] = (int32_t)normalize(tr, (p.flags & PF_TT) ? tt_max : 0, true);
@@ -2009,6 +2083,25 @@ __global__ void scatter_i64_kernel(int64_t *col, const uint64_t *idx, const int6
 
 // ------------------------------------------------------------- launchers
 
+// SPL_BAL: the filter pass and the score dump under a balanced list, for every
+// NodeResourcesFit variant (xf: SPL_XFIT as well)
+template <bool AFF>
+static void launch_filter_bal(const SpreadArgs &a, bool xf, uint32_t blocks, hipStream_t st) {
+  if (xf) {
+    if (a.fit_general == 2) spread_filter_kernel<AFF, false, 2, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_filter_kernel<AFF, false, 1, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  } else if (a.fit_general == 2) spread_filter_kernel<AFF, false, 2, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  else if (a.fit_general) spread_filter_kernel<AFF, false, 1, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  else spread_filter_kernel<AFF, false, 0, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+}
+static void launch_dump_bal(const SpreadArgs &a, bool xf, uint32_t blocks, hipStream_t st) {
+  if (xf) {
+    if (a.fit_general == 2) spread_select_kernel<false, 2, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_select_kernel<false, 1, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  } else if (a.fit_general == 2) spread_select_kernel<true, 0, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  else spread_select_kernel<false, 0, true><<<blocks, SP_THREADS, 0, st>>>(a);
+}
+
 hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_t st) {
   // node passes: at most SPREAD_MAX_BLOCKS blocks (248 measured no better)
   const uint32_t blocks =
@@ -2031,7 +2124,13 @@ hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_
   // SPL_XFIT: a listed extended resource in the pod's records (never with the
   // default strategy or a window: the setter refuses both)
   const bool xf = (passes & SPL_XFIT) && a.fit_general && !a.win_mode;
-  if (xf) {
+  // SPL_BAL: a scalar resource of the balanced list in the pod's records (never
+  // with a window: the setter refuses it)
+  const bool bal = (passes & SPL_BAL) && (a.bal_lo | a.bal_hi) && !a.win_mode;
+  if (bal) {
+    if (passes & SPL_AFF) launch_filter_bal<true>(a, xf, blocks, st);
+    else launch_filter_bal<false>(a, xf, blocks, st);
+  } else if (xf) {
     if (a.fit_general == 2) {
       if (passes & SPL_AFF) spread_filter_kernel<true, false, 2, true><<<blocks, SP_THREADS, 0, st>>>(a);
       else spread_filter_kernel<false, false, 2, true><<<blocks, SP_THREADS, 0, st>>>(a);
@@ -2046,7 +2145,8 @@ hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_
   } else if (passes & SPL_AFF) spread_filter_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
   else spread_filter_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
   if (passes & SPL_SCORE) spread_score_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
-  if (xf && a.dump) {
+  if (bal && a.dump) launch_dump_bal(a, xf, blocks, st);
+  else if (xf && a.dump) {
     if (a.fit_general == 2) spread_select_kernel<false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
     else spread_select_kernel<false, 1><<<blocks, SP_THREADS, 0, st>>>(a);
   } else if (a.fit_general == 2 && a.dump) spread_select_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);

@@ -325,6 +325,7 @@ class KsFitResource(C.Structure):  # ks_fit_resource (ks_set_fit_strategy_resour
 
 
 FIT_MAX_RESOURCES = 8  # extended resources a strategy may list
+BALANCED_MAX_RESOURCES = 10  # names a balanced list may hold: cpu, memory and 8 scalar resources
 FIT_LEAST_ALLOCATED, FIT_MOST_ALLOCATED, FIT_REQUESTED_TO_CAPACITY_RATIO = 0, 1, 2
 FIT_TYPES = {"LeastAllocated": FIT_LEAST_ALLOCATED, "MostAllocated": FIT_MOST_ALLOCATED,
              "RequestedToCapacityRatio": FIT_REQUESTED_TO_CAPACITY_RATIO}
@@ -349,6 +350,7 @@ KSCHED_SYMBOLS = [
     "ks_debug_runs_started", "ks_next_start_index", "ks_debug_sweep_geometry",
     "ks_set_fit_strategy", "ks_get_fit_strategy", "ks_set_fit_strategy_shape", "ks_get_fit_shape", "ks_fit_shape_table",
     "ks_set_fit_strategy_resources", "ks_get_fit_resources",
+    "ks_set_balanced_resources", "ks_get_balanced_resources",
 ]
 KSGATHER_SYMBOLS = [
     "ksg_open", "ksg_close", "ksg_set_members", "ksg_record_and_wait", "ksg_pending", "ksg_fnv1_32", "ksg_target_index",
@@ -429,6 +431,8 @@ def ksched_lib() -> C.CDLL:
     L.ks_set_fit_strategy_resources.argtypes = [vp, P(KsFitStrategy), P(KsFitShapePoint), C.c_uint32, P(KsFitResource),
                                                 C.c_uint32]
     L.ks_get_fit_resources.argtypes = [vp, P(KsFitResource), C.c_uint32, P(C.c_uint32)]
+    L.ks_set_balanced_resources.argtypes = [vp, P(C.c_char_p), C.c_uint32]
+    L.ks_get_balanced_resources.argtypes = [vp, P(C.c_char_p), C.c_uint32, P(C.c_uint32)]
     L.ks_debug_counters.argtypes = [vp, P(C.c_uint64)]
     L.ks_debug_sweep_geometry.argtypes = [vp, C.c_int32, P(C.c_uint64)]
     L.ks_debug_set_profile.argtypes = [vp, C.c_int32]

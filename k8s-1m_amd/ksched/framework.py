@@ -119,13 +119,16 @@ class Scheduler:
                  nodes_per_lane: int = 4, world_size: int = 1, rank: int = 0, virtual_shards: int = 1,
                  weights: Optional[Dict[str, int]] = None, options: Optional[Dict[str, int]] = None,
                  percentage_of_nodes_to_score: int = 100, fit_strategy: str = "LeastAllocated",
-                 fit_resource_weights: Optional[Dict[str, int]] = None, fit_shape=None):
+                 fit_resource_weights: Optional[Dict[str, int]] = None, fit_shape=None,
+                 balanced_resources=None):
         """options: ks_config execution options by field name (_abi.OPTION_FIELDS),
         e.g. {"resolve_mode": _abi.RESOLVE_SERIAL, "dedup_identical_pods": 0};
         none of them changes a result.  percentage_of_nodes_to_score: the
         profile's percentageOfNodesToScore (ksched.h; below 100 one shard only).
         fit_strategy / fit_resource_weights / fit_shape:
-        NodeResourcesFitArgs.scoringStrategy (set_fit_strategy)."""
+        NodeResourcesFitArgs.scoringStrategy (set_fit_strategy).
+        balanced_resources: NodeResourcesBalancedAllocationArgs.resources, an
+        ordered list of names (set_balanced_resources)."""
         self.lib = _abi.ksched_lib()
         cfg = _abi.KsConfig()
         self.lib.ks_config_default(C.byref(cfg))
@@ -166,6 +169,30 @@ class Scheduler:
             except Exception:
                 self.close()
                 raise
+        if balanced_resources is not None:
+            try:
+                self.set_balanced_resources(balanced_resources)
+            except Exception:
+                self.close()
+                raise
+
+    def set_balanced_resources(self, resources=None):
+        """NodeResourcesBalancedAllocationArgs.resources: the ordered names the
+        plugin balances, e.g. ["cpu", "memory", "amd.com/gpu"]; a scalar
+        resource is scored for the pods that request it, and the order is the
+        float64 summation order.  None or an empty list restores ["cpu",
+        "memory"].  Applies to every batch run after the call
+        (ks_set_balanced_resources, which judges the names)."""
+        names = [str(r).encode() for r in (resources or [])]
+        arr = (C.c_char_p * max(1, len(names)))(*names)
+        self._ok(self.lib.ks_set_balanced_resources(self.ctx, arr if names else None, len(names)))
+
+    def get_balanced_resources(self):
+        """The list in force, ["cpu", "memory"] by default."""
+        arr = (C.c_char_p * _abi.BALANCED_MAX_RESOURCES)()
+        n = C.c_uint32()
+        self._ok(self.lib.ks_get_balanced_resources(self.ctx, arr, _abi.BALANCED_MAX_RESOURCES, C.byref(n)))
+        return [arr[i].decode() for i in range(n.value)]
 
     def set_fit_strategy(self, strategy: str = "LeastAllocated", resource_weights: Optional[Dict[str, int]] = None,
                          shape=None):
