@@ -122,6 +122,19 @@ typedef struct {
   uint32_t _pad;
 } ks_node;
 
+/* v1.ContainerPort restricted to what NodePorts reads (upstream v1.31.3
+ * pkg/scheduler/framework/types.go HostPortInfo, plugins/nodeports).  NULL or
+ * "" for a string means the field is unset: host_ip then counts as "0.0.0.0"
+ * and protocol as "TCP" (HostPortInfo.sanitize).  Both are compared as
+ * strings: no IP normalisation, "tcp" is not "TCP".  An entry with
+ * host_port <= 0 is ignored. */
+typedef struct {
+  const char *host_ip;
+  const char *protocol;
+  int32_t host_port;
+  int32_t _pad;
+} ks_host_port;
+
 /* One container's resources.requests.  A resource that is ABSENT from the
  * requests map is distinguished from an explicit 0 (upstream
  * resourcehelper.PodRequests NonMissingContainerRequests semantics). */
@@ -136,6 +149,20 @@ typedef struct {
   const ks_resource *extended;  /* requests beyond cpu / memory (ephemeral-storage, scalar) */
   uint32_t n_extended;
   uint32_t _pad;
+  /* NodePorts: the container's ports (v1.Container.ports); entries with
+   * host_port <= 0 are ignored.  Read on ks_pod.containers only: init
+   * containers and sidecars do not count (NodeInfo.updateUsedPorts reads
+   * Spec.Containers alone).  On a pod bound through ks_pods_add /
+   * KS_EV_POD_ADD or a batch they become the node's used ports;
+   * ks_pods_remove / KS_EV_POD_REMOVE deletes them outright, as
+   * HostPortInfo.Remove does (no reference count).
+   * These three fields were appended within ABI 6: ks_container grew by 16
+   * bytes (48 to 64), no other field moved and ks_pod keeps its size.  Every
+   * caller must be rebuilt against this header and must zero-initialise the
+   * struct. */
+  const ks_host_port *host_ports;
+  uint32_t n_host_ports;
+  uint32_t _pad2;
 } ks_container;
 
 /* v1.NodeSelectorOperator */
@@ -233,7 +260,9 @@ typedef struct {
  * the shim falls back to upstream schedulePod for it.  The
  * default profile's plugins that read them: */
 enum {
-  KS_UNMODELLED_HOST_PORTS = 1u,       /* NodePorts: a container port with hostPort != 0             */
+  KS_UNMODELLED_HOST_PORTS = 1u,       /* NodePorts: host ports the caller could not express as
+                                          ks_container.host_ports (ksched models the plugin itself:
+                                          pass each container's ports there)                        */
   KS_UNMODELLED_TOPOLOGY_SPREAD = 2u,  /* PodTopologySpread constraints the caller could not express
                                           as ks_pod.spread (ksched models the plugin itself: pass the
                                           pod's constraints, or its system-default ones, there)      */
@@ -309,6 +338,12 @@ enum {
   KS_PLUGIN_INTER_POD_AFFINITY = 6,
   KS_NUM_FILTER_PLUGINS = 7
 };
+/* ks_node_score.status of a node whose first failing plugin is NodePorts
+ * (between NodeAffinity and NodeResourcesFit in the default filter order; a
+ * node failing both is NodePorts').  Not a KS_PLUGIN_* value: fail_counts keeps
+ * its eight entries and the count travels in ks_result.fail_node_ports.
+ * Values 0..6 and 7 (outside the PreFilterResult) keep their meaning. */
+enum { KS_STATUS_NODE_PORTS = 8 };
 
 enum {
   KS_POD_SCHEDULED = 0,     /* node_index valid                                  */
@@ -335,12 +370,14 @@ typedef struct {
   uint32_t fail_counts[KS_NUM_FAIL_COUNTS]; /* nodes rejected first by each filter plugin, then
                                                nodes excluded by the PreFilterResult */
   uint32_t flags;         /* KS_RESULT_*                                         */
-  uint32_t _pad;
+  uint32_t fail_node_ports; /* nodes rejected first by NodePorts (0 for a pod without host
+                               ports); this word was padding before                   */
 } ks_result;
 
 /* Per-node plugin scores of one pod (parity dump; NodePluginScores analogue). */
 typedef struct {
-  int32_t status;        /* -1 feasible, else KS_PLUGIN_* of the first failing filter, -2 empty slot */
+  int32_t status;        /* -1 feasible, else KS_PLUGIN_* of the first failing filter (KS_STATUS_NODE_PORTS
+                            for NodePorts), -2 empty slot */
   int32_t least_allocated;      /* NodeResourcesFit, under the strategy in force (ks_set_fit_strategy) */
   int32_t balanced_allocation;  /* NodeResourcesBalancedAllocation       */
   int32_t taint_raw;            /* TaintToleration raw (before normalize) */
@@ -553,6 +590,34 @@ ks_status ks_plugin_scores(ks_ctx *ctx, const ks_pod *pod, ks_node_score *out);
 
 /* Read back node resource state. */
 ks_status ks_node_states(ks_ctx *ctx, const uint32_t *slots, uint32_t n, ks_node_state *out);
+
+/* NodePorts.  ks_host_ports_conflict is pure host code and
+ * needs no context: 1 when a pod wanting `a` conflicts with a node holding `b`
+ * (HostPortInfo.CheckConflict against a set holding only b): both ports > 0
+ * and equal, the sanitised protocols equal, and the sanitised ips equal or
+ * either of them "0.0.0.0"; else 0 (also for a null argument).
+ * ks_node_used_ports reads back NodeInfo.UsedPorts of a slot from the device
+ * column, sanitised: *n entries (0 for an empty slot), copied to out when cap
+ * holds them; KS_ERR_INVALID, with *n set, when cap is below it (the
+ * convention of ks_get_fit_resources).  The strings belong to the context and
+ * stay valid until ks_close.  The call waits for submitted batches. */
+/* The dictionary: a context models 64 distinct sanitised (ip, protocol, port)
+ * triples and never frees one.  ks_batch_prepare interns a pod's triples as it
+ * compiles the batch, pod by pod: a batch refused part-way keeps the triples of
+ * the pods before the refused one.  ks_pods_check and ks_plugin_scores intern
+ * nothing.  ks_pods_check judges each pod on its own: two pods that each bring
+ * a new triple when 63 are in use both pass it, and a batch holding both is
+ * refused at the second (KS_ERR_CAPACITY).
+ * A bound pod (ks_pods_add / KS_EV_POD_ADD) with a triple the full dictionary
+ * cannot take is counted, and while the count is non-zero every pod with host
+ * ports is refused (KS_ERR_UNSUPPORTED).  The count is a count, not a record
+ * of pods: it falls by one for every removed pod that holds a triple the
+ * dictionary lacks, so add and remove calls must be paired, as the informer
+ * delivers them (removing a pod that was never added can clear a count another
+ * pod still justifies); a node deleted with such a pod on it leaves the count
+ * standing. */
+int32_t ks_host_ports_conflict(const ks_host_port *a, const ks_host_port *b);
+ks_status ks_node_used_ports(ks_ctx *ctx, uint32_t slot, ks_host_port *out, uint32_t cap, uint32_t *n);
 
 /* Cross-GPU candidate gather over RCCL (replaces CollectScore fan-in,
  * dist-scheduler/cmd/dist-scheduler/grpc_server.go:116-127 and

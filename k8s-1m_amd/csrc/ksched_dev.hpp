@@ -27,6 +27,11 @@ constexpr int ST_EMPTY = -2;
 // Outside NodeAffinity's PreFilterResult: no Filter plugin runs on the node
 // and no plugin is blamed (ks_result.fail_counts[KS_FAIL_PREFILTER_RESULT]).
 constexpr int ST_PREFILTERED = 7;
+// NodePorts (one-pod path only; KS_STATUS_NODE_PORTS): between NodeAffinity and
+// NodeResourcesFit in the first-failure order, counted beside the plugins'
+// counters (SpreadAccShard::fail_ports -> ks_result.fail_node_ports).
+constexpr int ST_NODE_PORTS = 8;
+constexpr int MAX_PORT_ENTRIES = 64;  // distinct (ip, protocol, port) triples of a context: one bit each
 
 // ---------------------------------------------------------- node table (SoA)
 // Columns are indexed by POSITION, not slot: a shard's slots are permuted so
@@ -154,7 +159,12 @@ struct alignas(16) SoloHdr {
   uint32_t n_containers;  // ImageLocality: len(initContainers) + len(containers)
   uint32_t n_aff;         // InterPodAffinity records
   uint32_t aff_flags;     // AFF_SELF
-  uint32_t _pad[2];
+  // NodePorts: the pod's wanted host ports as bits of the context's dictionary
+  // (entries are never freed, so the bits stay valid).  The host reads them
+  // when the chain is launched and resolves the conflict mask against the
+  // dictionary as it is then (SpreadArgs::ports_conflict); no
+  // kernel reads this word.  It was padding: no record moves.
+  uint64_t ports;
 };
 // InterPodAffinity (interpodaffinity/filtering.go, scoring.go): one record per
 // (term, count column) the pod's cycle reads.  Counts are summed per topology
@@ -213,7 +223,8 @@ struct SpreadAccShard {
   uint32_t fail[NFILT + 2];            // first failures per plugin (+ PodTopologySpread, InterPodAffinity)
   uint32_t feasible, ignored;          // feasible nodes; feasible nodes PreScore ignores
   uint32_t tt_max, na_max;             // max raw TaintToleration / NodeAffinity over feasible nodes
-  uint64_t pts_min, pts_max;           // raw PodTopologySpread min / max over non-ignored feasible nodes
+  uint32_t fail_ports;                 // first failures of NodePorts (in the alignment hole: no member moves)
+  uint64_t pts_min, pts_max;          // raw PodTopologySpread min / max over non-ignored feasible nodes
   uint64_t ipa_min, ipa_max;           // raw InterPodAffinity min / max over feasible nodes (biased 2^63)
   uint64_t best;                       // packed key of the winner
 };
@@ -305,9 +316,10 @@ struct DevResult {
   uint32_t ipa_fail;     // ks_result.fail_counts[KS_PLUGIN_INTER_POD_AFFINITY]
   uint32_t prefiltered;  // ks_result.fail_counts[KS_FAIL_PREFILTER_RESULT]
   uint32_t flags;
-  uint32_t _pad;
+  uint32_t fail_node_ports;  // ks_result.fail_node_ports (the one-pod chain's commit writes it; 0 elsewhere)
 };
 static_assert(sizeof(DevResult) == 64, "DevResult layout");
+static_assert(sizeof(SpreadAccShard) == 88, "SpreadAccShard layout");
 
 struct Weights {
   int32_t fit, ba, tt, na, il;

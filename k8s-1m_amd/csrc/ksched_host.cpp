@@ -335,6 +335,7 @@ struct ks_batch {
   bool any_spread = false;
   std::vector<uint8_t> xcols;  // per pod: the extended-resource columns its program requests, as a bit mask
   std::vector<uint32_t> xrecs;  // per pod: the record (XResDev) of each such column, 4 bits per column
+  std::vector<uint64_t> ports;  // per pod: its wanted host ports as dictionary bits (SoloHdr::ports)
   // replica runs: 1 the run kernel models the pod's program,
   // 2 the pod is identical to the one before it (program, labels)
   std::vector<uint8_t> rep;
@@ -502,6 +503,7 @@ struct ks_ctx {
   uint32_t next_bit = 0, next_num = 0;
   uint64_t label_resets = 0, taint_rebuilds = 0;  // dictionary capacity reclaims (diagnostics)
   std::unordered_map<uint32_t, std::vector<uint32_t>> key_nodes;  // key id -> slots having it
+  bool compile_for_dump = false;    // ks_plugin_scores' compile: host ports are never interned (PORTS_DUMP)
   bool compile_used_names = false;  // set by compile_pod when a pod resolved a node name to a slot
   uint32_t dict_version = 1;   // taint dictionary / node image set (compiled masks and checks)
   // Normaliser guesses (PodDev::tt_guess / na_guess): the distinct (label
@@ -527,6 +529,22 @@ struct ks_ctx {
   std::unordered_map<uint32_t, uint32_t> xres_of;
   std::vector<uint32_t> xres_names;
   int64_t *d_xalloc = nullptr, *d_xreq = nullptr;  // [MAX_XRES][npos], one allocation
+  // NodePorts: the distinct sanitised (ip, protocol, port)
+  // triples the context has seen, one bit of d_used_ports each.  Entries are
+  // never freed (a prepared batch holds their bits) and never move (the
+  // strings are handed out by ks_node_used_ports).  port_conf[i]: the entries
+  // a pod wanting entry i conflicts with, kept current as entries arrive and
+  // read when a chain is launched.  port_overflow: bound pods holding a triple
+  // the full dictionary could not take; while > 0 pods with host ports are refused.
+  struct PortEntry {
+    std::string ip, proto;
+    int32_t port = 0;
+  };
+  PortEntry port_entries[MAX_PORT_ENTRIES];
+  uint32_t n_port_entries = 0;
+  uint64_t port_conf[MAX_PORT_ENTRIES] = {};
+  int64_t port_overflow = 0;
+  uint64_t *d_used_ports = nullptr;  // [npos] NodeInfo.UsedPorts as dictionary bits (allocated with the first entry)
   // bound pods carrying pod (anti-)affinity terms (InterPodAffinity precondition)
   int64_t affinity_pods = 0;
   // PodTopologySpread (ksched_spread.hip; device columns allocated on first use)
@@ -1757,6 +1775,129 @@ ks_status pod_xrequests(ks_ctx *c, const ks_pod &p, bool create, std::vector<std
   return KS_OK;
 }
 
+// ------------------------------------------------------------- NodePorts
+// (upstream v1.31.3 framework/types.go HostPortInfo, plugins/nodeports;
+// DESIGN.md §5.13)
+
+// HostPortInfo.sanitize
+std::string port_ip(const char *s) { return s && s[0] ? s : "0.0.0.0"; }
+std::string port_proto(const char *s) { return s && s[0] ? s : "TCP"; }
+
+// Dictionary index of a triple, -1 when absent.
+int32_t port_find(const ks_ctx *c, const ks_host_port &hp) {
+  const std::string ip = port_ip(hp.host_ip), pr = port_proto(hp.protocol);
+  for (uint32_t i = 0; i < c->n_port_entries; ++i) {
+    const ks_ctx::PortEntry &e = c->port_entries[i];
+    if (e.port == hp.host_port && e.ip == ip && e.proto == pr) return (int32_t)i;
+  }
+  return -1;
+}
+
+// The used-ports column, with the first entry.
+ks_status ports_alloc(ks_ctx *c) {
+  if (c->d_used_ports) return KS_OK;
+  if (c->undrained) return KS_NEED_DRAIN;
+  HIPC(c, c->res.dev((void **)&c->d_used_ports, (size_t)c->npos * 8));
+  HIPC(c, hipMemsetAsync(c->d_used_ports, 0, (size_t)c->npos * 8, c->stream));
+  return KS_OK;
+}
+
+// Intern a triple: *out its index, or -1 when the dictionary is full.  A new
+// entry's conflicts with every entry (itself included) are recorded both
+// ways by the ABI's own predicate.
+ks_status port_intern(ks_ctx *c, const ks_host_port &hp, int32_t *out) {
+  if ((*out = port_find(c, hp)) >= 0) return KS_OK;
+  if (c->n_port_entries >= (uint32_t)MAX_PORT_ENTRIES) return KS_OK;
+  if (ks_status st = ports_alloc(c)) return st;
+  const uint32_t i = c->n_port_entries++;
+  ks_ctx::PortEntry &e = c->port_entries[i];
+  e.ip = port_ip(hp.host_ip);
+  e.proto = port_proto(hp.protocol);
+  e.port = hp.host_port;
+  auto abi = [](const ks_ctx::PortEntry &q) { return ks_host_port{q.ip.c_str(), q.proto.c_str(), q.port, 0}; };
+  const ks_host_port mine = abi(e);
+  c->port_conf[i] = 0;
+  for (uint32_t j = 0; j <= i; ++j) {
+    const ks_host_port other = abi(c->port_entries[j]);
+    if (ks_host_ports_conflict(&mine, &other)) c->port_conf[i] |= 1ull << j;
+    if (ks_host_ports_conflict(&other, &mine)) c->port_conf[j] |= 1ull << i;
+  }
+  *out = (int32_t)i;
+  return KS_OK;
+}
+
+// The host ports of a pod's containers (NodeInfo.updateUsedPorts: Spec.Containers
+// alone; entries with host_port <= 0 are ignored) as dictionary bits.
+//   PORTS_COMPILE  intern; a full dictionary: KS_ERR_CAPACITY
+//   PORTS_CHECK    look up only; KS_ERR_CAPACITY when the new triples would not fit
+//   PORTS_BIND     intern; *missing counts the triples a full dictionary could not take
+//   PORTS_FIND     look up only (a removal never interns); *missing counts the absent ones
+//   PORTS_DUMP     no lookup: *bits is the conflict mask itself, every entry a wanted port conflicts
+//                  with (the score dump is read-only and takes none of the 64 entries)
+enum PortsMode { PORTS_COMPILE, PORTS_CHECK, PORTS_BIND, PORTS_FIND, PORTS_DUMP };
+bool pod_lists_ports(const ks_pod &p) {  // some container carries port entries (cheap pre-check)
+  for (uint32_t i = 0; i < p.n_containers; ++i)
+    if (p.containers[i].n_host_ports) return true;
+  return false;
+}
+// The port entries of Spec.Containers with host_port > 0, in order: the one
+// place that walks and validates them (a count without an array: KS_ERR_INVALID).
+using PortList = std::vector<const ks_host_port *>;
+ks_status pod_port_entries(ks_ctx *c, const ks_pod &p, PortList *out) {
+  out->clear();
+  for (uint32_t i = 0; i < p.n_containers; ++i) {
+    const ks_container &k = p.containers[i];
+    if (k.n_host_ports && !k.host_ports)
+      return c->fail(KS_ERR_INVALID, "pod %s/%s: container %u has n_host_ports without host_ports", str(p.ns).c_str(),
+                     str(p.name).c_str(), i);
+    for (uint32_t j = 0; j < k.n_host_ports; ++j)
+      if (k.host_ports[j].host_port > 0) out->push_back(&k.host_ports[j]);
+  }
+  return KS_OK;
+}
+ks_status pod_ports(ks_ctx *c, const ks_pod &p, const PortList &all, PortsMode mode, uint64_t *bits, uint32_t *missing) {
+  *bits = 0;
+  if (missing) *missing = 0;
+  std::vector<ks_ctx::PortEntry> fresh;  // PORTS_CHECK: distinct triples the dictionary lacks
+  for (const ks_host_port *hpp : all) {
+    const ks_host_port &hp = *hpp;
+    if (mode == PORTS_DUMP) {
+      for (uint32_t j = 0; j < c->n_port_entries; ++j) {
+        const ks_ctx::PortEntry &e = c->port_entries[j];
+        const ks_host_port held{e.ip.c_str(), e.proto.c_str(), e.port, 0};
+        if (ks_host_ports_conflict(&hp, &held)) *bits |= 1ull << j;
+      }
+      continue;
+    }
+    int32_t i = -1;
+    if (mode == PORTS_COMPILE || mode == PORTS_BIND) {
+      if (ks_status st = port_intern(c, hp, &i)) return st;
+    } else {
+      i = port_find(c, hp);
+    }
+    if (i >= 0) {
+      *bits |= 1ull << i;
+      continue;
+    }
+    if (mode == PORTS_COMPILE)
+      return c->fail(KS_ERR_CAPACITY, "pod %s/%s: host port %s/%s:%d is the context's %dth distinct (ip, protocol, port)",
+                     str(p.ns).c_str(), str(p.name).c_str(), port_proto(hp.protocol).c_str(), port_ip(hp.host_ip).c_str(),
+                     hp.host_port, MAX_PORT_ENTRIES + 1);
+    if (mode == PORTS_CHECK) {
+      const ks_ctx::PortEntry e{port_ip(hp.host_ip), port_proto(hp.protocol), hp.host_port};
+      bool seen = false;
+      for (auto &f : fresh) seen |= f.port == e.port && f.ip == e.ip && f.proto == e.proto;
+      if (!seen) fresh.push_back(e);
+      if (c->n_port_entries + fresh.size() > (size_t)MAX_PORT_ENTRIES)
+        return c->fail(KS_ERR_CAPACITY, "pod %s/%s: host port %s/%s:%d does not fit the context's %d distinct (ip, protocol, port)",
+                       str(p.ns).c_str(), str(p.name).c_str(), e.proto.c_str(), e.ip.c_str(), e.port, MAX_PORT_ENTRIES);
+    } else if (missing) {
+      ++*missing;
+    }
+  }
+  return KS_OK;
+}
+
 // --------------------------------------------------------------- devices
 
 // A node's row of the table's label / taint columns as launch_scatter_rows
@@ -2347,7 +2488,7 @@ bool matched_by_terms(ks_ctx *c, const ks_pod &p) {
 // Whether compiling the pod may create one-pod-path state (columns, label
 // bits, device buffers): ks_batch_prepare drains the submitted batches first.
 bool may_need_solo(ks_ctx *c, const ks_pod &p) {
-  if (p.n_spread || p.n_affinity_terms || c->pct != 100) return true;
+  if (p.n_spread || p.n_affinity_terms || pod_lists_ports(p) || c->pct != 100) return true;
   if (matched_by_terms(c, p)) return true;
   for (uint32_t i = 0; i < p.n_containers; ++i)
     if (p.containers[i].n_extended || (!c->images.empty() && p.containers[i].image && p.containers[i].image[0]))
@@ -2446,6 +2587,7 @@ uint32_t solo_passes(const SoloHdr *hd) {
   for (uint32_t k = 0; k < hd->n_aff; ++k)
     if ((ad[k].kind & AF_KIND) != AF_OWN && !(ad[k].kind & AF_NODE)) f |= SPL_PREP;
   if (hd->n_aff) f |= SPL_AFF;  // the filter variant that reads the records
+  if (hd->ports) f |= SPL_PORTS;  // ... that reads the used ports
   return f;
 }
 
@@ -2536,7 +2678,8 @@ uint32_t ba_launch(SpreadArgs *sa, uint64_t by_col, uint8_t xcols, uint32_t xrec
 // move, for pods without a normalised TaintToleration / NodeAffinity score
 // (those maxima range over the feasible nodes, which change in such a run).
 bool replica_program(const PodDev &p, const SoloHdr *hd) {
-  if (hd->n_spread == 0 || hd->n_aff || hd->n_xres || hd->n_img || (p.flags & PF_PREF_ERR)) return false;
+  // (nor host ports: every commit of such a pod makes its node infeasible for the next)
+  if (hd->n_spread == 0 || hd->n_aff || hd->n_xres || hd->n_img || hd->ports || (p.flags & PF_PREF_ERR)) return false;
   const SpreadDev *sd = reinterpret_cast<const SpreadDev *>(hd + 1);
   uint32_t host = 0, other = 0;
   bool dns = false;
@@ -2592,6 +2735,23 @@ ks_status solo_compile(ks_ctx *c, const ks_pod &p, PodDev &d, ProgBuf &cl, bool 
   ks_status st;
   std::vector<std::pair<uint32_t, int64_t>> xr;
   if ((st = pod_xrequests(c, p, create, &xr))) return st;
+  // NodePorts: the wanted host ports as dictionary bits (nodeports.PreFilter: with none the plugin is skipped)
+  PortList want;
+  if ((st = pod_port_entries(c, p, &want))) return st;
+  const bool has_ports = !want.empty();
+  uint64_t ports = 0;
+  if (has_ports) {
+    if (c->pct != 100)
+      return c->fail(KS_ERR_UNSUPPORTED, "pod %s: host ports with percentage_of_nodes_to_score < 100", pn.c_str());
+    if (c->port_overflow > 0)
+      return c->fail(KS_ERR_UNSUPPORTED,
+                     "%lld bound pod(s) hold host ports beyond the %d distinct (ip, protocol, port) a context models: "
+                     "NodePorts cannot see them", (long long)c->port_overflow, MAX_PORT_ENTRIES);
+    // (the score dump is read-only: it interns nothing and its program carries the conflict mask itself,
+    // taken against the dictionary as it is now -- the dump is launched within the same call)
+    const PortsMode mode = !create ? PORTS_CHECK : c->compile_for_dump ? PORTS_DUMP : PORTS_COMPILE;
+    if ((st = pod_ports(c, p, want, mode, &ports, nullptr))) return st;
+  }
   // imagelocality#sumImageScores: every init and regular container whose
   // (normalised) image some node reports adds scaledImageScore
   std::vector<ImageDev> imgs;
@@ -2624,7 +2784,7 @@ ks_status solo_compile(ks_ctx *c, const ks_pod &p, PodDev &d, ProgBuf &cl, bool 
     if ((st = ipa_compile(c, p, create, refs, &aff, &aff_flags))) return st;
   }
   // (percentageOfNodesToScore < 100: every pod takes the chain, which holds the window pass)
-  if (!p.n_spread && xr.empty() && imgs.empty() && aff.empty() && c->pct == 100) return KS_OK;
+  if (!p.n_spread && xr.empty() && imgs.empty() && aff.empty() && !has_ports && c->pct == 100) return KS_OK;
   // multi-rank contexts run the one-pod path replicated: every rank holds the
   // whole node table and every commit, so each rank's chain over
   // all positions gives the same result with no exchange
@@ -2697,7 +2857,7 @@ ks_status solo_compile(ks_ctx *c, const ks_pod &p, PodDev &d, ProgBuf &cl, bool 
     std::memcpy(cl.w.data() + w0, rec, bytes);
   };
   const SoloHdr hdr{(uint32_t)recs.size(), (uint32_t)xr.size(), (uint32_t)imgs.size(),
-                    p.n_init_containers + p.n_containers, (uint32_t)aff.size(), aff_flags, {0, 0}};
+                    p.n_init_containers + p.n_containers, (uint32_t)aff.size(), aff_flags, ports};
   emit(&hdr, sizeof hdr);
   for (const SpreadDev &r : recs) emit(&r, sizeof r);
   for (auto &x : xr) {
@@ -3415,6 +3575,13 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
     if (b->any_spread && b->spread[lo]) {
       SpreadArgs sa = spread_args(c);
       const uint64_t ba_cols = ba_columns(c);
+      // NodePorts: every entry's conflicts against the dictionary as it is now (a batch prepared
+      // later may have interned a triple a pod of this one conflicts with)
+      uint64_t port_conf[MAX_PORT_ENTRIES];
+      {
+        std::lock_guard<std::mutex> g(c->mu);
+        std::memcpy(port_conf, c->port_conf, sizeof port_conf);
+      }
       sa.pods = b->d_pods;
       sa.clauses = b->d_clauses;
       sa.cmask = b->d_cmask;
@@ -3437,6 +3604,9 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
           e1 = get_event(c);
           HIPC(c, hipEventRecord(e0, c->stream));
         }
+        sa.ports_add = b->ports[i];
+        sa.ports_conflict = 0;
+        for (uint64_t m = b->ports[i]; m; m &= m - 1) sa.ports_conflict |= port_conf[__builtin_ctzll(m)];
         HIPC(c, launch_spread_pod(sa, (b->spread[i] & 0x7Fu) | xfit_launch(&sa, b->xcols[i]) |
                                           ba_launch(&sa, ba_cols, b->xcols[i], b->xrecs[i]),
                                   c->stream));
@@ -4154,7 +4324,7 @@ ks_status ks_nodes_delete(ks_ctx *c, const uint32_t *slots, uint32_t n) {
     core[(size_t)i * 8 + 3] = 1;   // reset requested state
   }
   if (!n) return KS_OK;
-  const size_t bytes = (size_t)n * 4 + core.size() * 8 + 1024;
+  const size_t bytes = (size_t)n * 4 + core.size() * 8 + (size_t)n * 8 + 2048;
   ks_status st = xfer_begin(c, bytes, bytes);
   if (st) return st;
   uint32_t *d_pos = dscratch<uint32_t>(c, n);
@@ -4162,6 +4332,12 @@ ks_status ks_nodes_delete(ks_ctx *c, const uint32_t *slots, uint32_t n) {
   if ((st = h2d(c, d_pos, pos.data(), (size_t)n * 4)) || (st = h2d(c, d_core, core.data(), core.size() * 8)))
     return st;
   HIPC(c, launch_scatter_rows(c->t, d_pos, d_core, nullptr, n, 0u, c->stream));
+  if (c->d_used_ports) {  // NodeInfo.UsedPorts leaves with the node
+    const std::vector<uint64_t> all(n, ~0ull);
+    uint64_t *d_all = dscratch<uint64_t>(c, n);
+    if ((st = h2d(c, d_all, all.data(), (size_t)n * 8))) return st;
+    HIPC(c, launch_ports_update(c->d_used_ports, d_pos, d_all, n, true, c->stream));
+  }
   if ((st = xfer_sync(c))) return st;
   if (!c->xres_names.empty()) {  // extended Allocatable / Requested leave with the node
     std::vector<uint64_t> idx;
@@ -4194,6 +4370,11 @@ static ks_status pods_delta(ks_ctx *c, const ks_pod *const *pods, const uint32_t
   std::vector<int64_t> xval;
   std::vector<std::pair<uint32_t, int64_t>> xr;
   std::vector<uint32_t> sets(n);
+  // NodeInfo.UsedPorts (validated and interned before any device work)
+  std::vector<uint32_t> ppos;
+  std::vector<uint64_t> pbits;
+  PortList pwant;
+  int64_t port_over = 0;
   // term classes held until the bound counts are applied (released on every return)
   struct Hold {
     ks_ctx *c;
@@ -4217,8 +4398,8 @@ static ks_status pods_delta(ks_ctx *c, const ks_pod *const *pods, const uint32_t
         if (slots[i] >= c->cap || !c->present_map[slots[i]]) continue;
         const ks_pod &pd = *pods[i];
         if (pd.n_namespace_labels || pd.n_affinity_terms || pd.n_labels) continue;
-        bool ext = false;
-        for (uint32_t k = 0; k < pd.n_containers; ++k) ext |= pd.containers[k].n_extended != 0;
+        bool ext = false;  // (or host ports: the serial loop interns them)
+        for (uint32_t k = 0; k < pd.n_containers; ++k) ext |= pd.containers[k].n_extended != 0 || pd.containers[k].n_host_ports != 0;
         for (uint32_t k = 0; k < pd.n_init_containers; ++k) ext |= pd.init_containers[k].n_extended != 0;
         if (ext) continue;
         auto it = c->empty_set_of_ns.find(str(pd.ns));  // read-only here: no thread interns
@@ -4255,6 +4436,19 @@ static ks_status pods_delta(ks_ctx *c, const ks_pod *const *pods, const uint32_t
       xval.push_back(sign * x.second);
     }
     if (pd.unmodelled & KS_UNMODELLED_POD_AFFINITY) aff += sign;
+    if ((st = pod_port_entries(c, pd, &pwant))) return st;
+    if (!pwant.empty()) {
+      // NodeInfo.updateUsedPorts: the pod's entries set, or deleted outright.  A triple the full
+      // dictionary cannot take makes the pod one NodePorts cannot see (port_overflow)
+      uint64_t bits;
+      uint32_t missing;
+      if ((st = pod_ports(c, pd, pwant, sign > 0 ? PORTS_BIND : PORTS_FIND, &bits, &missing))) return st;
+      if (missing) port_over += sign;
+      if (bits) {
+        ppos.push_back(c->slot_pos[slots[i]]);
+        pbits.push_back(bits);
+      }
+    }
     pos[i] = c->slot_pos[slots[i]];
     int64_t *x = &d[(size_t)i * 5];
     x[0] = sign * rc;
@@ -4263,13 +4457,21 @@ static ks_status pods_delta(ks_ctx *c, const ks_pod *const *pods, const uint32_t
     x[3] = sign * zm;
     x[4] = sign;
   }
-  const size_t bytes = (size_t)n * 4 + d.size() * 8 + 1024;
+  const size_t bytes = (size_t)n * 4 + d.size() * 8 + ppos.size() * 12 + 2048;
   ks_status st = xfer_begin(c, bytes, bytes);
   if (st) return st;
   uint32_t *d_pos = dscratch<uint32_t>(c, n);
   int64_t *d_d = dscratch<int64_t>(c, d.size());
   if ((st = h2d(c, d_pos, pos.data(), (size_t)n * 4)) || (st = h2d(c, d_d, d.data(), d.size() * 8))) return st;
   HIPC(c, launch_apply_deltas(c->t, d_pos, d_d, n, c->stream));
+  if (!ppos.empty()) {
+    uint64_t *d_pbits = dscratch<uint64_t>(c, pbits.size());
+    uint32_t *d_ppos = dscratch<uint32_t>(c, ppos.size());
+    if ((st = h2d(c, d_pbits, pbits.data(), pbits.size() * 8)) || (st = h2d(c, d_ppos, ppos.data(), ppos.size() * 4)))
+      return st;
+    HIPC(c, launch_ports_update(c->d_used_ports, d_ppos, d_pbits, (uint32_t)ppos.size(), sign < 0, c->stream));
+  }
+  c->port_overflow = std::max<int64_t>(0, c->port_overflow + port_over);
   c->affinity_pods += aff;
   if ((st = xfer_sync(c))) return st;
   if ((st = xres_scatter(c, xidx, xval, true))) return st;
@@ -4528,6 +4730,7 @@ ks_status ks_batch_prepare(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_batch *
   b->spread.assign(n, 0);
   b->xcols.assign(n, 0);
   b->xrecs.assign(n, 0);
+  b->ports.assign(n, 0);
   b->any_spread = false;
   b->rep.assign(n, 0);
   for (uint32_t i = 0; i < n; ++i) {
@@ -4536,6 +4739,7 @@ ks_status ks_batch_prepare(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_batch *
     b->spread[i] = (uint8_t)(0x80u | solo_passes(hd));
     b->xcols[i] = solo_xcols(hd);
     b->xrecs[i] = solo_xrecs(hd);
+    b->ports[i] = hd->ports;
     b->any_spread = true;
     if (!replica_program(dev[i], hd)) continue;
     b->rep[i] = 1;
@@ -4655,6 +4859,7 @@ SpreadArgs spread_args(ks_ctx *c) {
   sa.cnt = c->d_cnt;
   sa.xalloc = c->d_xalloc;
   sa.xreq = c->d_xreq;
+  sa.used_ports = c->d_used_ports;
   sa.dcnt = c->d_dcnt;
   sa.dflag = c->d_dflag;
   sa.tcnt = c->d_tcnt;
@@ -4694,6 +4899,7 @@ ks_status spread_plugin_scores(ks_ctx *c, const PodDev &d, const ProgBuf &cl, ks
   sa.dump = d_out;
   sa.no_commit = 1;
   const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + d.solo_off);
+  sa.ports_conflict = hd->ports;  // (a dump's program holds the conflict mask: PORTS_DUMP; no commit, ports_add stays 0)
   HIPC(c, launch_spread_pod(sa, solo_passes(hd) | xfit_launch(&sa, solo_xcols(hd)) |
                                     ba_launch(&sa, ba_columns(c), solo_xcols(hd), solo_xrecs(hd)),
                             c->stream));
@@ -4732,7 +4938,10 @@ ks_status ks_plugin_scores(ks_ctx *c, const ks_pod *pod, ks_node_score *out) {
   ks_status st;
   {
     std::unique_lock<std::mutex> g(c->mu);
-    if ((st = compile_batch(c, pod, 1, &d, cl, g, true))) return st;
+    c->compile_for_dump = true;
+    st = compile_batch(c, pod, 1, &d, cl, g, true);
+    c->compile_for_dump = false;
+    if (st) return st;
     if ((st = upload_dirty_ext(c, c->xm))) return st;
   }
   if (cl.w.empty()) cl.w.push_back(0);
@@ -4814,6 +5023,36 @@ ks_status ks_node_states(ks_ctx *c, const uint32_t *slots, uint32_t n, ks_node_s
     s.pod_count = s.alloc_pods < 0 ? -1 : (int32_t)r[7];
     if (s.alloc_pods < 0) s = ks_node_state{0, 0, 0, 0, 0, 0, 0, -1};
     out[i] = s;
+  }
+  return KS_OK;
+}
+
+// HostPortInfo.CheckConflict(a) against a set holding b alone (both sanitised).
+int32_t ks_host_ports_conflict(const ks_host_port *a, const ks_host_port *b) {
+  if (!a || !b || a->host_port <= 0 || b->host_port <= 0 || a->host_port != b->host_port) return 0;
+  if (port_proto(a->protocol) != port_proto(b->protocol)) return 0;
+  const std::string ia = port_ip(a->host_ip), ib = port_ip(b->host_ip);
+  return ia == "0.0.0.0" || ib == "0.0.0.0" || ia == ib ? 1 : 0;
+}
+
+ks_status ks_node_used_ports(ks_ctx *c, uint32_t slot, ks_host_port *out, uint32_t cap, uint32_t *n) {
+  if (!c || !n || (cap && !out)) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  if (slot >= c->cap) return c->fail(KS_ERR_NOT_FOUND, "slot %u >= capacity", slot);
+  *n = 0;
+  if (!c->d_used_ports || !c->present_map[slot]) return KS_OK;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  uint64_t bits = 0;
+  ks_status st;
+  if ((st = xfer_begin(c, 1024, 0)) || (st = d2h(c, &bits, c->d_used_ports + c->slot_pos[slot], 8)) ||
+      (st = xfer_sync(c)))
+    return st;
+  *n = (uint32_t)__builtin_popcountll(bits);
+  if (cap < *n) return c->fail(KS_ERR_INVALID, "ks_node_used_ports: room for %u of %u entries", cap, *n);
+  uint32_t k = 0;
+  for (; bits; bits &= bits - 1) {
+    const ks_ctx::PortEntry &e = c->port_entries[__builtin_ctzll(bits)];
+    out[k++] = ks_host_port{e.ip.c_str(), e.proto.c_str(), e.port, 0};
   }
   return KS_OK;
 }

@@ -128,6 +128,7 @@ enum SpreadLaunch : uint32_t {
   SPL_AFF = 8u,    // InterPodAffinity records
   SPL_XFIT = 16u,  // the strategy in force lists an extended resource the pod requests (decided at launch)
   SPL_BAL = 32u,   // the balanced list in force names a scalar resource the pod requests (decided at launch)
+  SPL_PORTS = 64u, // the pod wants host ports (NodePorts; its masks are resolved at launch)
 };
 struct SpreadArgs {
   NodeTable t;
@@ -181,6 +182,17 @@ struct SpreadArgs {
   uint32_t win_mode;
   int32_t pct;
   uint32_t bal_hi;            // (bal_lo above)
+  // SPL_PORTS: NodeInfo.UsedPorts as one dictionary bit per
+  // (ip, protocol, port) triple and position, and the pod's two masks against
+  // the dictionary as it is when the chain is launched: the entries a wanted
+  // port conflicts with (ks_host_ports_conflict), and the pod's own entries,
+  // which the commit adds to the chosen node.  32 bytes, here: the members
+  // below move by 32 and keep their alignment and their order, fit_table
+  // stays last (the replica kernels load it with ReplicaArgs' head), so every
+  // earlier kernel reads the same arguments at shifted offsets
+  uint64_t *used_ports;       // [npos] (null until the context has seen a host port)
+  uint64_t ports_conflict, ports_add;
+  uint64_t _ports_pad;
   // SPL_XFIT: the strategy's weight of each extended-resource
   // column, 8 bits each (0: not listed), resolved when the chain is launched,
   // so a program compiled under one strategy scores under the run's; and the
@@ -242,6 +254,9 @@ hipError_t launch_add_u32(uint32_t *col, const uint64_t *idx, const int32_t *del
 hipError_t launch_umax_u32(uint32_t *dst, const uint32_t *src, uint32_t n, hipStream_t st);
 hipError_t launch_scatter_i64(int64_t *col, const uint64_t *idx, const int64_t *val, uint32_t n, bool add,
                               hipStream_t st);
+// used-ports column: col[pos[i]] |= bits[i] (clear: &= ~bits[i]); positions may repeat
+hipError_t launch_ports_update(uint64_t *col, const uint32_t *pos, const uint64_t *bits, uint32_t n, bool clear,
+                               hipStream_t st);
 
 hipError_t launch_norm_check(const RoundArgs &a, hipStream_t st);
 // Label-word variant of the label / taint sweep (sweep_kernel's LWU): the

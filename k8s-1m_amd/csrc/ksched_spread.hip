@@ -592,8 +592,16 @@ constexpr int RF = NFILT + 2, R_FEAS = RF, R_IGN = RF + 1, R_TT = RF + 2, R_NA =
 // the fit check's column values also go into the score (score_fit_x)
 // BAL: BalancedAllocation over a list that names a scalar resource the pod
 // requests (SPL_BAL; under every GF and XF): score_ba_list for score_ba
-template <bool AFF, bool PROBE = false, int GF = 0, bool XF = false, bool BAL = false>
+// PORTS: the pod wants host ports (SPL_PORTS; under every AFF / GF / XF / BAL
+// combination, never the probe pass: a window refuses such pods).  NodePorts
+// (upstream nodeports.Filter) sits between NodeAffinity and NodeResourcesFit:
+// a node whose used ports hold an entry one of the pod's wanted ports
+// conflicts with (a.ports_conflict, resolved at launch) fails it, unless an
+// earlier plugin failed the node first.  Its counter is reduced beside the
+// others' (s_rp, thread R_N + 1) so that no instance without PORTS changes.
+template <bool AFF, bool PROBE = false, int GF = 0, bool XF = false, bool BAL = false, bool PORTS = false>
 __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a) {
+  static_assert(!(PORTS && PROBE), "host ports: no window");
   __shared__ uint32_t s_seen[SP_LDS / 32];
   __shared__ uint32_t s_h[SP_LDS];
   __shared__ uint32_t s_off[MAX_SPREAD];
@@ -602,6 +610,7 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
   __shared__ uint32_t s_red[SP_THREADS / WAVE][R_N];
   __shared__ uint64_t s_r64[SP_THREADS / WAVE][2];
   __shared__ SoloLds s_solo;
+  __shared__ uint32_t s_rp[PORTS ? SP_THREADS / WAVE : 1];  // (referenced under PORTS alone)
   const PodDev p = a.pods[a.pod];
   stage_solo(a, p, s_solo);
   for (uint32_t i = threadIdx.x; i < SP_LDS / 32; i += SP_THREADS) s_seen[i] = 0;
@@ -665,6 +674,7 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
   uint32_t fails[RF] = {0, 0, 0, 0, 0, 0, 0};
   uint32_t feasible = 0, ignored = 0, tt_max = 0, na_max = 0;
   uint64_t ipa_mn = ~0ull, ipa_mx = 0;
+  uint32_t fail_ports = 0;  // PORTS: nodes NodePorts rejects first
   // percentageOfNodesToScore < 100: the probe pass (filter only, win_st) or
   // the pass over the window spread_window_kernel found
   constexpr bool probe = PROBE;  // (the launcher passes win_mode 1 exactly to this instantiation)
@@ -686,7 +696,11 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
     PosIn in;
     AffView av{s_aoff, s_h, {}, {}};
     if (AFF) aff_prefetch(a, ad, na, pos, av);
+    // PORTS: the node's used ports, issued with the row's other loads (load_pos waits for them all)
+    uint64_t used_ports = 0;
+    if constexpr (PORTS) used_ports = a.used_ports[pos];
     load_pos(a, sd, n, want_cnt, pos, true, in);
+    if constexpr (PORTS) asm volatile("" ::"v"(used_ports));
     const uint32_t slot = in.slot;
     if (slot == SLOT_NONE) continue;
     NodeRegs r;
@@ -731,6 +745,10 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
       continue;
     }
     int s = filter<true>(p, a.clauses, r, e);
+    if constexpr (PORTS) {
+      // NodePorts, before NodeResourcesFit (4): a node failing both is NodePorts'
+      if ((s == ST_FEASIBLE || s == 4) && (used_ports & a.ports_conflict)) s = ST_NODE_PORTS;
+    }
     FitXSum fx{0, 0};
     double bxf0 = -1.0, bxf1 = -1.0;  // BAL: the fractions of the pod's first records (score_ba_list)
     if (s == ST_FEASIBLE) {
@@ -835,6 +853,7 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
     } else {
 #pragma unroll
       for (int q = 0; q < RF; ++q) fails[q] += s == q ? 1u : 0u;  // ST_PREFILTERED: no plugin
+      if constexpr (PORTS) fail_ports += s == ST_NODE_PORTS ? 1u : 0u;
     }
     a.st[pos] = out;
   }
@@ -855,6 +874,10 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
     for (int q = 0; q < R_N; ++q) s_red[wid][q] = v[q];
     s_r64[wid][0] = ipa_mn;
     s_r64[wid][1] = ipa_mx;
+  }
+  if constexpr (PORTS) {
+    fail_ports = wave_sum(fail_ports);
+    if (lane == 0) s_rp[wid] = fail_ports;
   }
   __syncthreads();
   // flush the block's ScheduleAnyway domain counts
@@ -886,6 +909,13 @@ __global__ __launch_bounds__(SP_THREADS) void spread_filter_kernel(SpreadArgs a)
     SpreadAccShard &bp = acc_shard(a);
     if (mn != ~0ull) atomicMin((unsigned long long *)&bp.ipa_min, (unsigned long long)mn);
     if (mx) atomicMax((unsigned long long *)&bp.ipa_max, (unsigned long long)mx);
+  }
+  if constexpr (PORTS) {
+    if (threadIdx.x == R_N + 1) {
+      uint32_t t = s_rp[0];
+      for (int w = 1; w < SP_THREADS / WAVE; ++w) t += s_rp[w];
+      if (t) atomicAdd(&acc_shard(a).fail_ports, t);
+    }
   }
 }
 
@@ -1308,12 +1338,14 @@ __global__ void spread_commit_kernel(SpreadArgs a) {
   if (a.win_mode) {  // the visited nodes and the PreFilterResult's exclusions
     uint32_t v = tot.feasible + p.prefilter_out;
     for (int q = 0; q < NFILT + 2; ++q) v += tot.fail[q];
-    r.evaluated_nodes = v;
+    r.evaluated_nodes = v;  // (no NodePorts failures here: a window refuses pods with host ports)
   }
   for (int q = 0; q < NFILT; ++q) r.fail_counts[q] = tot.fail[q];
   r.spread_fail = tot.fail[PLUGIN_SPREAD];
   r.ipa_fail = tot.fail[PLUGIN_IPA];
-  r._pad = 0;
+  uint32_t fail_ports = 0;  // ks_result.fail_node_ports
+  for (int k = 0; k < ACC_SHARDS; ++k) fail_ports += acc.sh[k].fail_ports;
+  r.fail_node_ports = fail_ports;
   r.prefiltered = p.prefilter_out;
   r.flags = 0;
   if (tot.feasible > 0) {
@@ -1337,6 +1369,7 @@ __global__ void spread_commit_kernel(SpreadArgs a) {
         a.t.npods[pos] += 1;
         const XResDev *xr = xres_recs(a, p);
         for (uint32_t k = 0; k < solo_hdr(a, p).n_xres; ++k) a.xreq[(size_t)xr[k].col * a.npos + pos] += xr[k].req;
+        if (a.ports_add) a.used_ports[pos] |= a.ports_add;  // NodeInfo.updateUsedPorts (uniform: one thread)
         for (int w = 0; w < CMASK_WORDS; ++w) {
           uint64_t m = a.cmask[(size_t)a.pod * CMASK_WORDS + w];
           while (m) {
@@ -1365,6 +1398,7 @@ __global__ void spread_commit_kernel(SpreadArgs a) {
     SpreadAccShard &q = acc.sh[k];
     for (int f = 0; f < NFILT + 2; ++f) q.fail[f] = 0;
     q.feasible = q.ignored = q.tt_max = q.na_max = 0;
+    q.fail_ports = 0;
     q.pts_min = q.ipa_min = ~0ull;
     q.pts_max = q.ipa_max = 0;
     q.best = 0;
@@ -1767,7 +1801,7 @@ __global__ __launch_bounds__(RUN_THREADS) void replica_run_kernel(SpreadArgs a, 
       for (int q = 0; q < NFILT; ++q) res.fail_counts[q] = s_tot.fail[q];
       res.spread_fail = s_tot.fail[PLUGIN_SPREAD];
       res.ipa_fail = s_tot.fail[PLUGIN_IPA];
-      res._pad = 0;
+      res.fail_node_ports = 0;  // (a replica run's pods carry no host ports)
       res.prefiltered = p.prefilter_out;
       res.flags = 0;
       a.results[pod] = res;
@@ -1800,7 +1834,7 @@ __global__ __launch_bounds__(RUN_THREADS) void replica_run_kernel(SpreadArgs a, 
     for (int q = 0; q < NFILT; ++q) res_tpl.fail_counts[q] = s_tot.fail[q];
     res_tpl.spread_fail = s_tot.fail[PLUGIN_SPREAD];
     res_tpl.ipa_fail = s_tot.fail[PLUGIN_IPA];
-    res_tpl._pad = 0;
+    res_tpl.fail_node_ports = 0;
     res_tpl.prefiltered = p.prefilter_out;
     res_tpl.flags = F == 1 ? 1u : 0u;  // KS_RESULT_SINGLE_FEASIBLE
     const uint32_t ncls = s_ctl[2], cls0 = ncls > 0 ? s_cls[0] : 0u, cls1 = ncls > 1 ? s_cls[1] : 0u;
@@ -2081,7 +2115,38 @@ __global__ void scatter_i64_kernel(int64_t *col, const uint64_t *idx, const int6
   else col[idx[i]] = val[i];
 }
 
+// NodeInfo.updateUsedPorts of pods bound / removed outside a batch: the
+// entries' bits set, or cleared outright (HostPortInfo.Remove keeps no
+// reference count).  Atomic: several pods of one call may share a node.
+__global__ void ports_update_kernel(uint64_t *col, const uint32_t *pos, const uint64_t *bits, uint32_t n,
+                                    uint32_t clear) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (clear) atomicAnd((unsigned long long *)&col[pos[i]], (unsigned long long)~bits[i]);
+  else atomicOr((unsigned long long *)&col[pos[i]], (unsigned long long)bits[i]);
+}
+
 // ------------------------------------------------------------- launchers
+
+// SPL_PORTS: the filter pass of a pod with host ports, under every variant the
+// launcher below reaches without them
+template <bool AFF>
+static void launch_filter_ports(const SpreadArgs &a, bool xf, bool bal, uint32_t blocks, hipStream_t st) {
+  const uint32_t g = a.fit_general;
+  if (bal && xf) {
+    if (g == 2) spread_filter_kernel<AFF, false, 2, true, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_filter_kernel<AFF, false, 1, true, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  } else if (bal) {
+    if (g == 2) spread_filter_kernel<AFF, false, 2, false, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    else if (g) spread_filter_kernel<AFF, false, 1, false, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_filter_kernel<AFF, false, 0, false, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  } else if (xf) {
+    if (g == 2) spread_filter_kernel<AFF, false, 2, true, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+    else spread_filter_kernel<AFF, false, 1, true, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  } else if (g == 2) spread_filter_kernel<AFF, false, 2, false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  else if (g) spread_filter_kernel<AFF, false, 1, false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+  else spread_filter_kernel<AFF, false, 0, false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+}
 
 // SPL_BAL: the filter pass and the score dump under a balanced list, for every
 // NodeResourcesFit variant (xf: SPL_XFIT as well)
@@ -2127,7 +2192,11 @@ hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_
   // SPL_BAL: a scalar resource of the balanced list in the pod's records (never
   // with a window: the setter refuses it)
   const bool bal = (passes & SPL_BAL) && (a.bal_lo | a.bal_hi) && !a.win_mode;
-  if (bal) {
+  // SPL_PORTS: a pod with host ports (never with a window: such a context refuses the pod)
+  if ((passes & SPL_PORTS) && a.used_ports && !a.win_mode) {
+    if (passes & SPL_AFF) launch_filter_ports<true>(a, xf, bal, blocks, st);
+    else launch_filter_ports<false>(a, xf, bal, blocks, st);
+  } else if (bal) {
     if (passes & SPL_AFF) launch_filter_bal<true>(a, xf, blocks, st);
     else launch_filter_bal<false>(a, xf, blocks, st);
   } else if (xf) {
@@ -2214,6 +2283,13 @@ hipError_t launch_scatter_i64(int64_t *col, const uint64_t *idx, const int64_t *
                               hipStream_t st) {
   if (!n) return hipSuccess;
   scatter_i64_kernel<<<(n + 255) / 256, 256, 0, st>>>(col, idx, val, n, add ? 1u : 0u);
+  return hipGetLastError();
+}
+
+hipError_t launch_ports_update(uint64_t *col, const uint32_t *pos, const uint64_t *bits, uint32_t n, bool clear,
+                               hipStream_t st) {
+  if (!n) return hipSuccess;
+  ports_update_kernel<<<(n + 255) / 256, 256, 0, st>>>(col, pos, bits, n, clear ? 1u : 0u);
   return hipGetLastError();
 }
 

@@ -58,6 +58,10 @@ class KsNode(C.Structure):
     ]
 
 
+class KsHostPort(C.Structure):  # ks_host_port: None / b"" = unset (ip "0.0.0.0", protocol "TCP")
+    _fields_ = [("host_ip", c_char_p), ("protocol", c_char_p), ("host_port", C.c_int32), ("_pad", C.c_int32)]
+
+
 class KsContainer(C.Structure):
     _fields_ = [
         ("milli_cpu", C.c_int64),
@@ -68,6 +72,10 @@ class KsContainer(C.Structure):
         ("extended", C.POINTER(KsResource)),
         ("n_extended", C.c_uint32),
         ("_pad", C.c_uint32),
+        # NodePorts: the container's ports, appended within ABI 6 (ks_container grew by 16 bytes)
+        ("host_ports", C.POINTER(KsHostPort)),
+        ("n_host_ports", C.c_uint32),
+        ("_pad2", C.c_uint32),
     ]
 
 
@@ -169,6 +177,8 @@ class KsPod(C.Structure):
 
 NUM_FILTER_PLUGINS = 7
 NUM_FAIL_COUNTS = 8  # + KS_FAIL_PREFILTER_RESULT
+STATUS_NODE_PORTS = 8  # KS_STATUS_NODE_PORTS: ks_node_score.status of a node NodePorts rejects first
+MAX_PORT_ENTRIES = 64  # distinct (ip, protocol, port) triples a context models
 # ks_status codes and ks_event kinds (include/ksched.h)
 KS_OK, KS_ERR_INVALID, KS_ERR_DEVICE, KS_ERR_CAPACITY, KS_ERR_UNSUPPORTED, KS_ERR_RANGE = 0, 1, 2, 3, 4, 5
 KS_ERR_NOT_FOUND, KS_ERR_COMM, KS_ERR_STALE = 6, 7, 8
@@ -205,7 +215,7 @@ class KsResult(C.Structure):
         ("evaluated_nodes", C.c_uint32),
         ("fail_counts", C.c_uint32 * NUM_FAIL_COUNTS),
         ("flags", C.c_uint32),
-        ("_pad", C.c_uint32),
+        ("fail_node_ports", C.c_uint32),  # nodes rejected first by NodePorts (padding before)
     ]
 
 
@@ -306,8 +316,8 @@ class KsStats(C.Structure):
 
 # sizes from the C headers (checked in tests/test_abi.py against offsetof via the compiler)
 EXPECTED_SIZES = {
-    "ks_label": 16, "ks_taint": 24, "ks_toleration": 24, "ks_node": 88, "ks_container": 48,
-    "ks_resource": 16, "ks_image": 16,
+    "ks_label": 16, "ks_taint": 24, "ks_toleration": 24, "ks_node": 88, "ks_container": 64,
+    "ks_resource": 16, "ks_image": 16, "ks_host_port": 24,
     "ks_requirement": 24, "ks_term": 24, "ks_preferred_term": 32, "ks_pod": 184, "ks_event": 24, "ks_result": 64,
     "ks_node_score": 56, "ks_node_state": 56, "ks_config": 124, "ks_pod_affinity_term": 96, "ks_stats": 112, "ks_label_selector": 32,
     "ks_spread_constraint": 72,
@@ -338,7 +348,7 @@ STRUCTS = {
     "ks_node_score": KsNodeScore, "ks_node_state": KsNodeState, "ks_config": KsConfig,
     "ks_stats": KsStats, "ks_label_selector": KsLabelSelector, "ks_spread_constraint": KsSpreadConstraint,
     "ks_resource": KsResource, "ks_image": KsImage, "ks_pod_affinity_term": KsPodAffinityTerm,
-}
+}  # (ks_host_port, as the ks_fit_* structs: checked by tests/test_abi_ports.py, whose probe prints it)
 
 KSCHED_SYMBOLS = [
     "ks_config_default", "ks_open", "ks_close", "ks_last_error", "ks_abi_version", "ks_nodes_upsert",
@@ -351,6 +361,7 @@ KSCHED_SYMBOLS = [
     "ks_set_fit_strategy", "ks_get_fit_strategy", "ks_set_fit_strategy_shape", "ks_get_fit_shape", "ks_fit_shape_table",
     "ks_set_fit_strategy_resources", "ks_get_fit_resources",
     "ks_set_balanced_resources", "ks_get_balanced_resources",
+    "ks_host_ports_conflict", "ks_node_used_ports",
 ]
 KSGATHER_SYMBOLS = [
     "ksg_open", "ksg_close", "ksg_set_members", "ksg_record_and_wait", "ksg_pending", "ksg_fnv1_32", "ksg_target_index",
@@ -433,6 +444,8 @@ def ksched_lib() -> C.CDLL:
     L.ks_get_fit_resources.argtypes = [vp, P(KsFitResource), C.c_uint32, P(C.c_uint32)]
     L.ks_set_balanced_resources.argtypes = [vp, P(C.c_char_p), C.c_uint32]
     L.ks_get_balanced_resources.argtypes = [vp, P(C.c_char_p), C.c_uint32, P(C.c_uint32)]
+    L.ks_host_ports_conflict.argtypes = [P(KsHostPort), P(KsHostPort)]
+    L.ks_node_used_ports.argtypes = [vp, C.c_uint32, P(KsHostPort), C.c_uint32, P(C.c_uint32)]
     L.ks_debug_counters.argtypes = [vp, P(C.c_uint64)]
     L.ks_debug_sweep_geometry.argtypes = [vp, C.c_int32, P(C.c_uint64)]
     L.ks_debug_set_profile.argtypes = [vp, C.c_int32]

@@ -389,6 +389,8 @@ class Scheduler:
                                           r.feasible_nodes, r.node_index, r.total_score, bool(r.flags & 1)))
             elif r.status == 1:
                 counts = {FILTER_PLUGINS[k]: int(r.fail_counts[k]) for k in range(7) if r.fail_counts[k]}
+                if r.fail_node_ports:  # nodes whose first failing plugin is NodePorts (ks_result.fail_node_ports)
+                    counts["NodePorts"] = int(r.fail_node_ports)
                 out.append(FitError(f"pod#{i}", r.evaluated_nodes, Diagnosis(counts, set(counts))))
             else:
                 out.append(FrameworkError(f"pod#{i}: plugin Error status"))
@@ -428,6 +430,14 @@ class Scheduler:
         out = (_abi.KsNodeState * max(1, len(slots)))()
         self._ok(self.lib.ks_node_states(self.ctx, sl, len(slots), out))
         return list(out)[: len(slots)]
+
+    def node_used_ports(self, slot: int) -> List[tuple]:
+        """NodeInfo.UsedPorts of a slot, sanitised: [(hostIP, protocol, hostPort)]
+        (ks_node_used_ports; the device column's entries)."""
+        out = (_abi.KsHostPort * _abi.MAX_PORT_ENTRIES)()
+        n = C.c_uint32()
+        self._ok(self.lib.ks_node_used_ports(self.ctx, slot, out, _abi.MAX_PORT_ENTRIES, C.byref(n)))
+        return [(out[i].host_ip.decode(), out[i].protocol.decode(), int(out[i].host_port)) for i in range(n.value)]
 
     # ---------------------------------------------------------- batches
     def prepare(self, arr, n: int):

@@ -7,7 +7,7 @@ memory in bytes (Quantity.Value()).
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, Optional, Tuple
 
 from . import _abi
@@ -41,6 +41,8 @@ class Container:
     requests: Dict[str, int] = field(default_factory=dict)
     restart_policy_always: bool = False  # init containers: sidecar
     image: str = ""
+    # ports: (hostIP, protocol, hostPort) per port (NodePorts reads those of spec.containers alone)
+    host_ports: List[Tuple[Optional[str], Optional[str], int]] = field(default_factory=list)
 
 
 @dataclass
@@ -142,6 +144,11 @@ class Pod:
     spread_defaulted: bool = False  # topology_spread holds the system defaults (see ksched.h ks_pod)
     affinity_terms: List[PodAffinityTerm] = field(default_factory=list)
     namespace_labels: Dict[str, str] = field(default_factory=dict)
+    # NodePorts: (hostIP, protocol, hostPort) of every port of spec.containers, flattened (marshalled onto
+    # the first container's ks_container.host_ports); None / "" = unset (hostIP "0.0.0.0", protocol "TCP");
+    # entries with hostPort <= 0 are ignored.  pod_to_c appends them to containers[0].host_ports and raises
+    # ValueError for a pod that has none to carry them
+    host_ports: List[Tuple[Optional[str], Optional[str], int]] = field(default_factory=list)
 
 
 class Arena:
@@ -174,8 +181,11 @@ def _container(c: Container, a: "Arena") -> _abi.KsContainer:
         else:
             ext.append(_abi.KsResource(a.s(k), v))
     xs, nx = a.array(_abi.KsResource, ext)
+    hps, nhp = a.array(_abi.KsHostPort,
+                       [_abi.KsHostPort(a.s(ip), a.s(proto), port, 0) for ip, proto, port in c.host_ports])
     return _abi.KsContainer(c.requests.get("cpu", 0), c.requests.get("memory", 0), flags,
-                            1 if c.restart_policy_always else 0, a.s(c.image) if c.image else None, xs, nx, 0)
+                            1 if c.restart_policy_always else 0, a.s(c.image) if c.image else None, xs, nx, 0,
+                            hps if nhp else None, nhp, 0)
 
 
 def _requirement(r: NodeSelectorRequirement, a: Arena) -> _abi.KsRequirement:
@@ -228,7 +238,12 @@ def node_to_c(n: Node, a: Arena) -> _abi.KsNode:
 
 
 def pod_to_c(p: Pod, a: Arena) -> _abi.KsPod:
-    cs, ncs = a.array(_abi.KsContainer, [_container(c, a) for c in p.containers])
+    conts = list(p.containers)
+    if p.host_ports:  # the pod's flattened list travels on its first container (ks_container.host_ports)
+        if not conts:
+            raise ValueError(f"pod {p.name}: host ports without a container")
+        conts[0] = replace(conts[0], host_ports=list(conts[0].host_ports) + list(p.host_ports))
+    cs, ncs = a.array(_abi.KsContainer, [_container(c, a) for c in conts])
     ics, nics = a.array(_abi.KsContainer, [_container(c, a) for c in p.init_containers])
     tols, ntol = a.array(_abi.KsToleration, [
         _abi.KsToleration(a.s(t.key), a.s(t.value), TOL_OPS.get(t.operator, 2), EFFECTS.get(t.effect, 9))
