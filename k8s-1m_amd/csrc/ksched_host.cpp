@@ -299,6 +299,13 @@ enum ProfSlot {
   PROF_SLOTS
 };
 
+// What a one-pod program asks of the chain's launch (solo_needs walks its header).
+struct SoloNeeds {
+  uint32_t passes = 0;  // SpreadLaunch passes its records need
+  uint32_t xrecs = 0;   // the record (XResDev) of each extended-resource column it requests, 4 bits per column
+  uint8_t xcols = 0;    // those columns, as a bit mask
+};
+
 }  // namespace
 
 // ================================================================= context
@@ -333,8 +340,7 @@ struct ks_batch {
   std::vector<uint32_t> set_ids;
   std::vector<uint8_t> spread;
   bool any_spread = false;
-  std::vector<uint8_t> xcols;  // per pod: the extended-resource columns its program requests, as a bit mask
-  std::vector<uint32_t> xrecs;  // per pod: the record (XResDev) of each such column, 4 bits per column
+  std::vector<SoloNeeds> solo;  // per pod: what its one-pod program asks of the chain's launch
   std::vector<uint64_t> ports;  // per pod: its wanted host ports as dictionary bits (SoloHdr::ports)
   // replica runs: 1 the run kernel models the pod's program,
   // 2 the pod is identical to the one before it (program, labels)
@@ -2577,26 +2583,26 @@ ks_status ipa_compile(ks_ctx *c, const ks_pod &p, bool create, std::vector<uint3
   return KS_OK;
 }
 
-// Passes of the spread chain a one-pod program needs (SpreadLaunch).
-uint32_t solo_passes(const SoloHdr *hd) {
+// One walk of a one-pod program's records: the passes of the spread chain it
+// needs (SpreadLaunch), and the extended-resource columns it requests with
+// the record of each.
+SoloNeeds solo_needs(const SoloHdr *hd) {
+  SoloNeeds n;
   const SpreadDev *sd = reinterpret_cast<const SpreadDev *>(hd + 1);
-  uint32_t f = 0;
-  for (uint32_t k = 0; k < hd->n_spread; ++k) f |= (sd[k].flags & SP_SCORE) ? SPL_SCORE : (SPL_PREP | SPL_MIN);
-  const AffDev *ad = reinterpret_cast<const AffDev *>(reinterpret_cast<const uint8_t *>(sd + hd->n_spread) +
-                                                      hd->n_xres * sizeof(XResDev) + hd->n_img * sizeof(ImageDev));
+  for (uint32_t k = 0; k < hd->n_spread; ++k) n.passes |= (sd[k].flags & SP_SCORE) ? SPL_SCORE : (SPL_PREP | SPL_MIN);
+  const XResDev *xr = reinterpret_cast<const XResDev *>(sd + hd->n_spread);
+  for (uint32_t k = 0; k < hd->n_xres; ++k) {
+    const uint32_t col = xr[k].col & (MAX_XRES - 1);
+    n.xcols |= (uint8_t)(1u << col);
+    if (k < (uint32_t)MAX_XRES) n.xrecs |= k << (4 * col);
+  }
+  const AffDev *ad = reinterpret_cast<const AffDev *>(reinterpret_cast<const uint8_t *>(xr + hd->n_xres) +
+                                                      hd->n_img * sizeof(ImageDev));
   for (uint32_t k = 0; k < hd->n_aff; ++k)
-    if ((ad[k].kind & AF_KIND) != AF_OWN && !(ad[k].kind & AF_NODE)) f |= SPL_PREP;
-  if (hd->n_aff) f |= SPL_AFF;  // the filter variant that reads the records
-  if (hd->ports) f |= SPL_PORTS;  // ... that reads the used ports
-  return f;
-}
-
-// Extended-resource columns a one-pod program requests, as a bit mask.
-uint8_t solo_xcols(const SoloHdr *hd) {
-  const XResDev *xr = reinterpret_cast<const XResDev *>(reinterpret_cast<const SpreadDev *>(hd + 1) + hd->n_spread);
-  uint8_t m = 0;
-  for (uint32_t k = 0; k < hd->n_xres; ++k) m |= (uint8_t)(1u << (xr[k].col & (MAX_XRES - 1)));
-  return m;
+    if ((ad[k].kind & AF_KIND) != AF_OWN && !(ad[k].kind & AF_NODE)) n.passes |= SPL_PREP;
+  if (hd->n_aff) n.passes |= SPL_AFF;  // the filter variant that reads the records
+  if (hd->ports) n.passes |= SPL_PORTS;  // ... that reads the used ports
+  return n;
 }
 
 // The strategy's weight of every extended-resource column, 8 bits each
@@ -2619,15 +2625,6 @@ uint32_t xfit_launch(SpreadArgs *sa, uint8_t xcols) {
   if (!wx || !sa->fit_general) return 0;
   for (uint32_t k = 0; k < 4; ++k) sa->xrcp[k] = fit_weight_rcp(wx + (k & 1u ? sa->fs.wc : 0u) + (k & 2u ? sa->fs.wm : 0u));
   return SPL_XFIT;
-}
-
-// The record of each extended-resource column a one-pod program requests, 4
-// bits per column (with solo_xcols telling which columns are present).
-uint32_t solo_xrecs(const SoloHdr *hd) {
-  const XResDev *xr = reinterpret_cast<const XResDev *>(reinterpret_cast<const SpreadDev *>(hd + 1) + hd->n_spread);
-  uint32_t m = 0;
-  for (uint32_t k = 0; k < hd->n_xres && k < (uint32_t)MAX_XRES; ++k) m |= k << (4 * (xr[k].col & (MAX_XRES - 1)));
-  return m;
 }
 
 // The balanced list in force by column (ksched_ba.hpp's packing with a column
@@ -2665,6 +2662,12 @@ uint32_t ba_launch(SpreadArgs *sa, uint64_t by_col, uint8_t xcols, uint32_t xrec
   sa->bal_lo = scalar ? (uint32_t)l : 0u;
   sa->bal_hi = scalar ? (uint32_t)(l >> 32) : 0u;
   return scalar ? SPL_BAL : 0u;
+}
+
+// The passes of a chain launch for a program with the needs `n` under the
+// strategy of `sa` and the balanced list `ba_cols`, whose per-pod arguments it sets.
+uint32_t chain_passes(SpreadArgs *sa, uint64_t ba_cols, const SoloNeeds &n) {
+  return n.passes | xfit_launch(sa, n.xcols) | ba_launch(sa, ba_cols, n.xcols, n.xrecs);
 }
 
 // Replica runs: the run kernel models a one-pod program with at
@@ -3607,9 +3610,7 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
         sa.ports_add = b->ports[i];
         sa.ports_conflict = 0;
         for (uint64_t m = b->ports[i]; m; m &= m - 1) sa.ports_conflict |= port_conf[__builtin_ctzll(m)];
-        HIPC(c, launch_spread_pod(sa, (b->spread[i] & 0x7Fu) | xfit_launch(&sa, b->xcols[i]) |
-                                          ba_launch(&sa, ba_cols, b->xcols[i], b->xrecs[i]),
-                                  c->stream));
+        HIPC(c, launch_spread_pod(sa, chain_passes(&sa, ba_cols, b->solo[i]), c->stream));
         if (tm) {
           HIPC(c, hipEventRecord(e1, c->stream));
           c->ev_spread.emplace_back(e0, e1);
@@ -4728,17 +4729,15 @@ ks_status ks_batch_prepare(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_batch *
   b->class_refs = std::move(refs);
   b->term_refs = std::move(term_refs);
   b->spread.assign(n, 0);
-  b->xcols.assign(n, 0);
-  b->xrecs.assign(n, 0);
+  b->solo.assign(n, SoloNeeds{});
   b->ports.assign(n, 0);
   b->any_spread = false;
   b->rep.assign(n, 0);
   for (uint32_t i = 0; i < n; ++i) {
     if (!(dev[i].flags & PF_SOLO)) continue;
     const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + dev[i].solo_off);
-    b->spread[i] = (uint8_t)(0x80u | solo_passes(hd));
-    b->xcols[i] = solo_xcols(hd);
-    b->xrecs[i] = solo_xrecs(hd);
+    b->solo[i] = solo_needs(hd);
+    b->spread[i] = (uint8_t)(0x80u | b->solo[i].passes);
     b->ports[i] = hd->ports;
     b->any_spread = true;
     if (!replica_program(dev[i], hd)) continue;
@@ -4900,9 +4899,7 @@ ks_status spread_plugin_scores(ks_ctx *c, const PodDev &d, const ProgBuf &cl, ks
   sa.no_commit = 1;
   const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + d.solo_off);
   sa.ports_conflict = hd->ports;  // (a dump's program holds the conflict mask: PORTS_DUMP; no commit, ports_add stays 0)
-  HIPC(c, launch_spread_pod(sa, solo_passes(hd) | xfit_launch(&sa, solo_xcols(hd)) |
-                                    ba_launch(&sa, ba_columns(c), solo_xcols(hd), solo_xrecs(hd)),
-                            c->stream));
+  HIPC(c, launch_spread_pod(sa, chain_passes(&sa, ba_columns(c), solo_needs(hd)), c->stream));
   if ((st = d2h(c, raw.data(), d_out, raw.size() * 4)) || (st = xfer_sync(c))) return st;
   for (uint32_t i = 0; i < c->cap; ++i) {
     const int32_t *o = &raw[(size_t)i * SPREAD_DUMP_WORDS];
@@ -5224,58 +5221,113 @@ ks_status ks_debug_sweep_geometry(ks_ctx *c, int32_t ext, uint64_t out[8]) {
   return KS_OK;
 }
 
+ks_status ks_fit_shape_table(const ks_fit_shape_point *shape, uint32_t n, uint8_t out[101]) {
+  return fit_shape_table(shape, n, out) ? KS_OK : KS_ERR_INVALID;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ----- the scoring configuration: what its setters share
+
+using FitTable = uint8_t[FIT_TABLE_WORDS * 4];
+
+// A strategy's cpu and memory weights: 0..100 each, and not both 0 unless
+// extended resources are scored beside them (`both_zero`).
+bool fit_weights_ok(const ks_fit_strategy *s, bool both_zero) {
+  return s->weight_cpu >= 0 && s->weight_cpu <= 100 && s->weight_memory >= 0 && s->weight_memory <= 100 &&
+         (both_zero || s->weight_cpu != 0 || s->weight_memory != 0);
+}
+
+// T[0..100] of a shape, the tail of the 128-byte device copy repeating T[100].
+bool fit_table_build(const ks_fit_shape_point *shape, uint32_t n, FitTable &tab) {
+  if (!fit_shape_table(shape, n, tab)) return false;
+  for (uint32_t i = FIT_TABLE_N; i < sizeof tab; ++i) tab[i] = tab[FIT_TABLE_N - 1];
+  return true;
+}
+
+// The one-FMA floor's bound on every present node's Allocatable of each listed
+// scalar resource that has a column (empty positions hold 0).
+ks_status xres_columns_bounded(ks_ctx *c, const std::vector<std::string> &names) {
+  HIPC(c, hipSetDevice(c->cfg.device));
+  ks_status st;
+  std::vector<int64_t> colv;
+  for (const std::string &nm : names) {
+    if (nm == "cpu" || nm == "memory") continue;
+    const int32_t id = c->lookup(nm.c_str());
+    uint32_t col = UINT32_MAX;
+    {
+      std::lock_guard<std::mutex> g(c->mu);
+      auto it = id < 0 ? c->xres_of.end() : c->xres_of.find((uint32_t)id);
+      if (it != c->xres_of.end()) col = it->second;
+    }
+    if (col == UINT32_MAX) continue;
+    colv.resize(c->npos);
+    const size_t bytes = (size_t)c->npos * 8;
+    if ((st = xfer_begin(c, 1024, bytes + 1024)) || (st = d2h(c, colv.data(), c->d_xalloc + (size_t)col * c->npos, bytes)) ||
+        (st = xfer_sync(c)))
+      return st;
+    for (int64_t v : colv)
+      if (v >= kMaxAlloc)
+        return c->fail(KS_ERR_RANGE, "a node's allocatable of %s outside the exact range", nm.c_str());
+  }
+  return KS_OK;
+}
+
+// The end of every NodeResourcesFit setter, its arguments valid and no batch
+// running (the setter drained): the checks against the context, then the
+// strategy in force.  `tab` is the shape's table (RequestedToCapacityRatio
+// only), `names` the extended resources with the weights `extended[i].weight`.
+ks_status commit_fit(ks_ctx *c, const ks_fit_strategy &s, const ks_fit_shape_point *shape, uint32_t n_shape,
+                     const FitTable *tab, std::vector<std::string> names, const ks_fit_resource *extended) {
+  const bool rtcr = s.type == KS_FIT_REQUESTED_TO_CAPACITY_RATIO;
+  // an extended list makes the strategy general even over {LeastAllocated, 1, 1}
+  const bool general =
+      rtcr || !names.empty() || !(s.type == KS_FIT_LEAST_ALLOCATED && s.weight_cpu == 1 && s.weight_memory == 1);
+  // the window's only reference is the oracle's own schedule, which knows the default strategy alone
+  if (general && c->pct != 100) return KS_ERR_UNSUPPORTED;
+  ks_status st;
+  if (!names.empty() && (st = xres_columns_bounded(c, names))) return st;
+  // the device copy has no reader
+  if (rtcr && ((st = xfer_begin(c, 1024, 0)) || (st = h2d(c, c->d_fit_table, *tab, sizeof *tab)) || (st = xfer_sync(c))))
+    return st;
+  std::lock_guard<std::mutex> g(c->mu);
+  c->fit = ks_fit_strategy{s.type, s.weight_cpu, s.weight_memory, 0};
+  // RequestedToCapacityRatio rounds: math.Round(n / d) = floor((2 n + d) / (2 d)),
+  // so it takes the reciprocals of 2 d (fit_rtcr_node_score)
+  const uint32_t wc = (uint32_t)s.weight_cpu, wm = (uint32_t)s.weight_memory, m = rtcr ? 2u : 1u;
+  c->fit_params = FitParams{rtcr ? 2u : s.type == KS_FIT_MOST_ALLOCATED ? 1u : 0u, wc, wm, fit_weight_rcp(m * wc),
+                            fit_weight_rcp(m * wm), fit_weight_rcp(m * (wc + wm))};
+  c->fit_general = general ? m : 0u;
+  if (rtcr) c->fit_shape.assign(shape, shape + n_shape);
+  else c->fit_shape.clear();
+  c->fit_x.clear();
+  for (size_t i = 0; i < names.size(); ++i) c->fit_x.emplace_back(c->intern(names[i].c_str()), extended[i].weight);
+  c->fit_x_names = std::move(names);
+  return KS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 ks_status ks_set_fit_strategy(ks_ctx *c, const ks_fit_strategy *s) {
   if (!c || !s) return KS_ERR_INVALID;
   if (ks_status dst_ = drain_async(c)) return dst_;
   if (s->type != KS_FIT_LEAST_ALLOCATED && s->type != KS_FIT_MOST_ALLOCATED) return KS_ERR_INVALID;
-  if (s->weight_cpu < 0 || s->weight_cpu > 100 || s->weight_memory < 0 || s->weight_memory > 100 ||
-      (s->weight_cpu == 0 && s->weight_memory == 0))
-    return KS_ERR_INVALID;
-  const bool general = !(s->type == KS_FIT_LEAST_ALLOCATED && s->weight_cpu == 1 && s->weight_memory == 1);
-  // the window's only reference is the oracle's own schedule, which knows the default strategy alone
-  if (general && c->pct != 100) return KS_ERR_UNSUPPORTED;
-  std::lock_guard<std::mutex> g(c->mu);
-  c->fit = ks_fit_strategy{s->type, s->weight_cpu, s->weight_memory, 0};
-  const uint32_t wc = (uint32_t)s->weight_cpu, wm = (uint32_t)s->weight_memory;
-  c->fit_params = FitParams{s->type == KS_FIT_MOST_ALLOCATED ? 1u : 0u, wc, wm, fit_weight_rcp(wc), fit_weight_rcp(wm),
-                            fit_weight_rcp(wc + wm)};
-  c->fit_general = general ? 1u : 0u;
-  c->fit_shape.clear();
-  c->fit_x.clear();  // cpu and memory only
-  c->fit_x_names.clear();
-  return KS_OK;
-}
-
-ks_status ks_fit_shape_table(const ks_fit_shape_point *shape, uint32_t n, uint8_t out[101]) {
-  return fit_shape_table(shape, n, out) ? KS_OK : KS_ERR_INVALID;
+  if (!fit_weights_ok(s, false)) return KS_ERR_INVALID;
+  return commit_fit(c, *s, nullptr, 0, nullptr, {}, nullptr);
 }
 
 ks_status ks_set_fit_strategy_shape(ks_ctx *c, const ks_fit_strategy *s, const ks_fit_shape_point *shape, uint32_t n) {
   if (!c || !s) return KS_ERR_INVALID;
   if (ks_status dst_ = drain_async(c)) return dst_;
   if (s->type != KS_FIT_REQUESTED_TO_CAPACITY_RATIO) return shape || n ? KS_ERR_INVALID : ks_set_fit_strategy(c, s);
-  if (s->weight_cpu < 0 || s->weight_cpu > 100 || s->weight_memory < 0 || s->weight_memory > 100 ||
-      (s->weight_cpu == 0 && s->weight_memory == 0))
-    return KS_ERR_INVALID;
-  // T[0..100], the tail of the 128-byte copy repeating T[100]
-  uint8_t tab[FIT_TABLE_WORDS * 4];
-  if (!fit_shape_table(shape, n, tab)) return KS_ERR_INVALID;
-  for (uint32_t i = FIT_TABLE_N; i < sizeof tab; ++i) tab[i] = tab[FIT_TABLE_N - 1];
-  // as ks_set_fit_strategy: no reference for the window under another strategy
-  if (c->pct != 100) return KS_ERR_UNSUPPORTED;
-  // no batch runs (drained above): the device copy has no reader
-  ks_status st;
-  if ((st = xfer_begin(c, 1024, 0)) || (st = h2d(c, c->d_fit_table, tab, sizeof tab)) || (st = xfer_sync(c))) return st;
-  std::lock_guard<std::mutex> g(c->mu);
-  c->fit = ks_fit_strategy{s->type, s->weight_cpu, s->weight_memory, 0};
-  const uint32_t wc = (uint32_t)s->weight_cpu, wm = (uint32_t)s->weight_memory;
-  // math.Round(n / d) = floor((2 n + d) / (2 d)): the reciprocals of 2 d (fit_rtcr_node_score)
-  c->fit_params = FitParams{2u, wc, wm, fit_weight_rcp(2 * wc), fit_weight_rcp(2 * wm), fit_weight_rcp(2 * (wc + wm))};
-  c->fit_general = 2u;
-  c->fit_shape.assign(shape, shape + n);
-  c->fit_x.clear();  // cpu and memory only
-  c->fit_x_names.clear();
-  return KS_OK;
+  if (!fit_weights_ok(s, false)) return KS_ERR_INVALID;
+  FitTable tab;
+  if (!fit_table_build(shape, n, tab)) return KS_ERR_INVALID;
+  return commit_fit(c, *s, shape, n, &tab, {}, nullptr);
 }
 
 ks_status ks_set_fit_strategy_resources(ks_ctx *c, const ks_fit_strategy *s, const ks_fit_shape_point *shape,
@@ -5287,14 +5339,9 @@ ks_status ks_set_fit_strategy_resources(ks_ctx *c, const ks_fit_strategy *s, con
   const bool rtcr = s->type == KS_FIT_REQUESTED_TO_CAPACITY_RATIO;
   if (!rtcr && s->type != KS_FIT_LEAST_ALLOCATED && s->type != KS_FIT_MOST_ALLOCATED) return KS_ERR_INVALID;
   // cpu and memory may both be left out: the extended resources are scored
-  if (s->weight_cpu < 0 || s->weight_cpu > 100 || s->weight_memory < 0 || s->weight_memory > 100) return KS_ERR_INVALID;
-  uint8_t tab[FIT_TABLE_WORDS * 4];
-  if (rtcr) {
-    if (!fit_shape_table(shape, n_shape, tab)) return KS_ERR_INVALID;
-    for (uint32_t i = FIT_TABLE_N; i < sizeof tab; ++i) tab[i] = tab[FIT_TABLE_N - 1];
-  } else if (shape || n_shape) {
-    return KS_ERR_INVALID;
-  }
+  if (!fit_weights_ok(s, true)) return KS_ERR_INVALID;
+  FitTable tab;
+  if (rtcr ? !fit_table_build(shape, n_shape, tab) : shape || n_shape) return KS_ERR_INVALID;
   if (n_extended > (uint32_t)MAX_XRES)
     return c->fail(KS_ERR_INVALID, "more than %d extended resources in the strategy", MAX_XRES);
   bool ephemeral = false;
@@ -5313,47 +5360,7 @@ ks_status ks_set_fit_strategy_resources(ks_ctx *c, const ks_fit_strategy *s, con
   // upstream scores ephemeral-storage for every pod, requesting or not: a
   // column of the round kernels, which is not modelled
   if (ephemeral) return c->fail(KS_ERR_UNSUPPORTED, "ephemeral-storage in the strategy's resources");
-  // as ks_set_fit_strategy: no reference for the window under another strategy
-  if (c->pct != 100) return KS_ERR_UNSUPPORTED;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  ks_status st;
-  // the one-FMA floor's bound on every present node's Allocatable of a listed
-  // name (empty positions hold 0)
-  std::vector<int64_t> colv;
-  for (const std::string &nm : names) {
-    const int32_t id = c->lookup(nm.c_str());
-    uint32_t col = UINT32_MAX;
-    {
-      std::lock_guard<std::mutex> g(c->mu);
-      auto it = id < 0 ? c->xres_of.end() : c->xres_of.find((uint32_t)id);
-      if (it != c->xres_of.end()) col = it->second;
-    }
-    if (col == UINT32_MAX) continue;
-    colv.resize(c->npos);
-    const size_t bytes = (size_t)c->npos * 8;
-    if ((st = xfer_begin(c, 1024, bytes + 1024)) || (st = d2h(c, colv.data(), c->d_xalloc + (size_t)col * c->npos, bytes)) ||
-        (st = xfer_sync(c)))
-      return st;
-    for (int64_t v : colv)
-      if (v >= kMaxAlloc)
-        return c->fail(KS_ERR_RANGE, "a node's allocatable of %s outside the exact range", nm.c_str());
-  }
-  // no batch runs (drained above): the device copy has no reader
-  if (rtcr && ((st = xfer_begin(c, 1024, 0)) || (st = h2d(c, c->d_fit_table, tab, sizeof tab)) || (st = xfer_sync(c))))
-    return st;
-  std::lock_guard<std::mutex> g(c->mu);
-  c->fit = ks_fit_strategy{s->type, s->weight_cpu, s->weight_memory, 0};
-  const uint32_t wc = (uint32_t)s->weight_cpu, wm = (uint32_t)s->weight_memory, m = rtcr ? 2u : 1u;
-  c->fit_params = FitParams{rtcr ? 2u : s->type == KS_FIT_MOST_ALLOCATED ? 1u : 0u, wc, wm, fit_weight_rcp(m * wc),
-                            fit_weight_rcp(m * wm), fit_weight_rcp(m * (wc + wm))};
-  // an extended list makes the strategy general even over {LeastAllocated, 1, 1}
-  c->fit_general = m;
-  if (rtcr) c->fit_shape.assign(shape, shape + n_shape);
-  else c->fit_shape.clear();
-  c->fit_x.clear();
-  for (uint32_t i = 0; i < n_extended; ++i) c->fit_x.emplace_back(c->intern(names[i].c_str()), extended[i].weight);
-  c->fit_x_names = std::move(names);
-  return KS_OK;
+  return commit_fit(c, *s, shape, n_shape, &tab, std::move(names), extended);
 }
 
 ks_status ks_set_balanced_resources(ks_ctx *c, const char *const *names, uint32_t n) {
@@ -5381,32 +5388,9 @@ ks_status ks_set_balanced_resources(ks_ctx *c, const char *const *names, uint32_
   if (ephemeral) return c->fail(KS_ERR_UNSUPPORTED, "ephemeral-storage in the balanced list");
   if (n && (!cpu || !mem)) return c->fail(KS_ERR_UNSUPPORTED, "a balanced list without cpu or memory");
   const bool dflt = !n || (n == 2 && list[0] == "cpu");
-  // as ks_set_fit_strategy: no reference for the window under another list
+  // as commit_fit: no reference for the window under another list
   if (!dflt && c->pct != 100) return KS_ERR_UNSUPPORTED;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  ks_status st;
-  // the bound on every present node's Allocatable of a listed name, as
-  // ks_set_fit_strategy_resources checks it
-  std::vector<int64_t> colv;
-  for (const std::string &nm : list) {
-    if (nm == "cpu" || nm == "memory") continue;
-    const int32_t id = c->lookup(nm.c_str());
-    uint32_t col = UINT32_MAX;
-    {
-      std::lock_guard<std::mutex> g(c->mu);
-      auto it = id < 0 ? c->xres_of.end() : c->xres_of.find((uint32_t)id);
-      if (it != c->xres_of.end()) col = it->second;
-    }
-    if (col == UINT32_MAX) continue;
-    colv.resize(c->npos);
-    const size_t bytes = (size_t)c->npos * 8;
-    if ((st = xfer_begin(c, 1024, bytes + 1024)) || (st = d2h(c, colv.data(), c->d_xalloc + (size_t)col * c->npos, bytes)) ||
-        (st = xfer_sync(c)))
-      return st;
-    for (int64_t v : colv)
-      if (v >= kMaxAlloc)
-        return c->fail(KS_ERR_RANGE, "a node's allocatable of %s outside the exact range", nm.c_str());
-  }
+  if (ks_status st = xres_columns_bounded(c, list)) return st;
   std::lock_guard<std::mutex> g(c->mu);
   c->ba_list.clear();
   c->ba_names.clear();

@@ -33,6 +33,9 @@
 // (zones), with global atomics only for high-cardinality ones (hostnames).
 #include <hip/hip_runtime.h>
 
+#include <array>
+#include <utility>
+
 #include "ksched_ba.hpp"
 #include "ksched_dev.hpp"
 #include "ksched_eval.hpp"
@@ -2128,50 +2131,62 @@ __global__ void ports_update_kernel(uint64_t *col, const uint32_t *pos, const ui
 
 // ------------------------------------------------------------- launchers
 
-// SPL_PORTS: the filter pass of a pod with host ports, under every variant the
-// launcher below reaches without them
-template <bool AFF>
-static void launch_filter_ports(const SpreadArgs &a, bool xf, bool bal, uint32_t blocks, hipStream_t st) {
-  const uint32_t g = a.fit_general;
-  if (bal && xf) {
-    if (g == 2) spread_filter_kernel<AFF, false, 2, true, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_filter_kernel<AFF, false, 1, true, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  } else if (bal) {
-    if (g == 2) spread_filter_kernel<AFF, false, 2, false, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    else if (g) spread_filter_kernel<AFF, false, 1, false, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_filter_kernel<AFF, false, 0, false, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  } else if (xf) {
-    if (g == 2) spread_filter_kernel<AFF, false, 2, true, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_filter_kernel<AFF, false, 1, true, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  } else if (g == 2) spread_filter_kernel<AFF, false, 2, false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  else if (g) spread_filter_kernel<AFF, false, 1, false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  else spread_filter_kernel<AFF, false, 0, false, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
-}
+// The chain's kernel variants, by their template switches.  Which combinations
+// exist: XF (a listed extended resource in NodeResourcesFit) needs a general
+// strategy, GF >= 1; PROBE (the window's probe pass) takes no other switch
+// but AFF, so its two instances are launched by name and are not in a table;
+// RT (RequestedToCapacityRatio in the select) appears only for a score dump
+// under GF 2 without XF, a dump with XF carrying the strategy in XG instead.
+// Every other combination of AFF, GF, XF, BAL and PORTS is an instance.
+using SpreadKernel = void (*)(SpreadArgs);
 
-// SPL_BAL: the filter pass and the score dump under a balanced list, for every
-// NodeResourcesFit variant (xf: SPL_XFIT as well)
-template <bool AFF>
-static void launch_filter_bal(const SpreadArgs &a, bool xf, uint32_t blocks, hipStream_t st) {
-  if (xf) {
-    if (a.fit_general == 2) spread_filter_kernel<AFF, false, 2, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_filter_kernel<AFF, false, 1, true, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  } else if (a.fit_general == 2) spread_filter_kernel<AFF, false, 2, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  else if (a.fit_general) spread_filter_kernel<AFF, false, 1, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  else spread_filter_kernel<AFF, false, 0, false, true><<<blocks, SP_THREADS, 0, st>>>(a);
+// spread_filter_kernel<AFF, false, GF, XF, BAL, PORTS> at filter_index(...)
+constexpr uint32_t filter_index(bool aff, uint32_t gf, bool xf, bool bal, bool ports) {
+  return (aff ? 1u : 0u) | (xf ? 2u : 0u) | (bal ? 4u : 0u) | (ports ? 8u : 0u) | gf << 4;
 }
-static void launch_dump_bal(const SpreadArgs &a, bool xf, uint32_t blocks, hipStream_t st) {
-  if (xf) {
-    if (a.fit_general == 2) spread_select_kernel<false, 2, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_select_kernel<false, 1, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  } else if (a.fit_general == 2) spread_select_kernel<true, 0, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  else spread_select_kernel<false, 0, true><<<blocks, SP_THREADS, 0, st>>>(a);
+template <uint32_t I>
+constexpr SpreadKernel filter_variant() {
+  constexpr int GF = I >> 4;
+  constexpr bool XF = I & 2u;
+  if constexpr (XF && GF == 0) return nullptr;
+  else return spread_filter_kernel<(I & 1u) != 0, false, GF, XF, (I & 4u) != 0, (I & 8u) != 0>;
 }
+// spread_select_kernel<RT, XG, BAL> at BAL | sel << 1: sel 0 the plain select,
+// 1 / 2 a dump with XF under GF 1 / 2, 3 a dump under GF 2 without XF (RT)
+template <uint32_t I>
+constexpr SpreadKernel select_variant() {
+  constexpr uint32_t sel = I >> 1;
+  return spread_select_kernel<sel == 3, sel == 3 ? 0 : (int)sel, (I & 1u) != 0>;
+}
+template <uint32_t... I>
+constexpr std::array<SpreadKernel, sizeof...(I)> filter_variants(std::integer_sequence<uint32_t, I...>) {
+  return {filter_variant<I>()...};
+}
+template <uint32_t... I>
+constexpr std::array<SpreadKernel, sizeof...(I)> select_variants(std::integer_sequence<uint32_t, I...>) {
+  return {select_variant<I>()...};
+}
+constexpr auto kFilterVariants = filter_variants(std::make_integer_sequence<uint32_t, filter_index(true, 2, true, true, true) + 1>{});
+constexpr auto kSelectVariants = select_variants(std::make_integer_sequence<uint32_t, 8>{});
 
 hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_t st) {
   // node passes: at most SPREAD_MAX_BLOCKS blocks (248 measured no better)
   const uint32_t blocks =
       std::max<uint32_t>(1, std::min<uint32_t>((args.npos + SP_THREADS - 1) / SP_THREADS, (uint32_t)SPREAD_MAX_BLOCKS));
   const SpreadArgs &a = args;
+  // SPL_XFIT: a listed extended resource in the pod's records (never with the
+  // default strategy or a window: the setter refuses both)
+  const bool xf = (passes & SPL_XFIT) && a.fit_general && !a.win_mode;
+  // SPL_BAL: a scalar resource of the balanced list in the pod's records (never
+  // with a window: the setter refuses it)
+  const bool bal = (passes & SPL_BAL) && (a.bal_lo | a.bal_hi) && !a.win_mode;
+  // SPL_PORTS: a pod with host ports (never with a window: such a context refuses the pod)
+  const bool ports = (passes & SPL_PORTS) && a.used_ports && !a.win_mode;
+  const uint32_t gf = a.fit_general == 2 ? 2u : a.fit_general ? 1u : 0u;
+  const SpreadKernel filter = kFilterVariants[filter_index(passes & SPL_AFF, gf, xf, bal, ports)];
+  if (!filter) return hipErrorInvalidValue;
+  // the select knows the strategy only to dump NodeResourcesFit's score
+  const SpreadKernel select = kSelectVariants[!a.dump ? 0u : (bal ? 1u : 0u) | (xf ? gf : gf == 2 ? 3u : 0u) << 1];
   if (passes & SPL_PREP) spread_prep_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
   if (passes & SPL_MIN) spread_min_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
   if (a.win_mode) {  // percentageOfNodesToScore < 100: probe, window, then the pass over the window
@@ -2186,40 +2201,9 @@ hipError_t launch_spread_pod(const SpreadArgs &args, uint32_t passes, hipStream_
     spread_wcount_kernel<<<(a.nslots + WIN_CHUNK - 1) / WIN_CHUNK, WIN_CHUNK / 16, 0, st>>>(a);
     spread_window_kernel<<<1, WIN_THREADS, 0, st>>>(a);
   }
-  // SPL_XFIT: a listed extended resource in the pod's records (never with the
-  // default strategy or a window: the setter refuses both)
-  const bool xf = (passes & SPL_XFIT) && a.fit_general && !a.win_mode;
-  // SPL_BAL: a scalar resource of the balanced list in the pod's records (never
-  // with a window: the setter refuses it)
-  const bool bal = (passes & SPL_BAL) && (a.bal_lo | a.bal_hi) && !a.win_mode;
-  // SPL_PORTS: a pod with host ports (never with a window: such a context refuses the pod)
-  if ((passes & SPL_PORTS) && a.used_ports && !a.win_mode) {
-    if (passes & SPL_AFF) launch_filter_ports<true>(a, xf, bal, blocks, st);
-    else launch_filter_ports<false>(a, xf, bal, blocks, st);
-  } else if (bal) {
-    if (passes & SPL_AFF) launch_filter_bal<true>(a, xf, blocks, st);
-    else launch_filter_bal<false>(a, xf, blocks, st);
-  } else if (xf) {
-    if (a.fit_general == 2) {
-      if (passes & SPL_AFF) spread_filter_kernel<true, false, 2, true><<<blocks, SP_THREADS, 0, st>>>(a);
-      else spread_filter_kernel<false, false, 2, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    } else if (passes & SPL_AFF) spread_filter_kernel<true, false, 1, true><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_filter_kernel<false, false, 1, true><<<blocks, SP_THREADS, 0, st>>>(a);
-  } else if (a.fit_general == 2) {
-    if (passes & SPL_AFF) spread_filter_kernel<true, false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_filter_kernel<false, false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
-  } else if (a.fit_general) {
-    if (passes & SPL_AFF) spread_filter_kernel<true, false, 1><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_filter_kernel<false, false, 1><<<blocks, SP_THREADS, 0, st>>>(a);
-  } else if (passes & SPL_AFF) spread_filter_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
-  else spread_filter_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
+  filter<<<blocks, SP_THREADS, 0, st>>>(a);
   if (passes & SPL_SCORE) spread_score_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
-  if (bal && a.dump) launch_dump_bal(a, xf, blocks, st);
-  else if (xf && a.dump) {
-    if (a.fit_general == 2) spread_select_kernel<false, 2><<<blocks, SP_THREADS, 0, st>>>(a);
-    else spread_select_kernel<false, 1><<<blocks, SP_THREADS, 0, st>>>(a);
-  } else if (a.fit_general == 2 && a.dump) spread_select_kernel<true><<<blocks, SP_THREADS, 0, st>>>(a);
-  else spread_select_kernel<false><<<blocks, SP_THREADS, 0, st>>>(a);
+  select<<<blocks, SP_THREADS, 0, st>>>(a);
   spread_commit_kernel<<<1, WAVE, 0, st>>>(a);
   return hipGetLastError();
 }

@@ -9,6 +9,7 @@ import functools
 import numpy as np
 
 import xfit_workloads as X
+from ba_reference import BaReference
 from fit_reference import LEAST, MOST
 from ksched.objects import Container, Node, Pod
 from rtcr_reference import SHAPES
@@ -35,6 +36,10 @@ def configure(s, case):
     strategy, extended, balanced = CASES[case]
     X.set_strategy(s, strategy, extended)
     s.set_balanced_resources(balanced)
+
+
+def two_rank_case(cfg):
+    return X.replicated_case(93, lambda cap: BaReference(cap, *CASES[cfg["case"]]), lambda s: configure(s, cfg["case"]))
 
 
 # ---------------------------------------------------------------- the grid

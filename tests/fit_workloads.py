@@ -138,6 +138,24 @@ def hetero_reference(kind_name, strategy_name):
     return out
 
 
+def hetero_case(w, want, states, configure):
+    """The stream `w` as a two-rank case (tests/chain_multirank_main.py): two calls, each rank configured alike."""
+    m = w["m"]
+
+    def setup(s):
+        configure(s)
+        hetero_setup(s, w)
+
+    return dict(capacity=N_H, pods_per_round=P_H, setup=setup, want=res_array(want, m), states=states,
+                batches=[(pods_at(w["ps"].pods, a), b - a) for a, b in ((0, m // 2), (m // 2, m))])
+
+
+def two_rank_case(cfg):
+    kind, wc, wm = STRATEGIES[cfg["strategy_name"]]
+    return hetero_case(hetero_stream(cfg["kind_name"]), *hetero_reference(cfg["kind_name"], cfg["strategy_name"]),
+                       lambda s: s.set_fit_strategy(kind, {"cpu": wc, "memory": wm}))
+
+
 # --------------------------------------- the widening label-dictionary batches
 @functools.lru_cache(maxsize=None)
 def wide_reference(strategy_name):

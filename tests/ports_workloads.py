@@ -19,9 +19,11 @@ import functools
 import itertools
 import random
 
+from fit_reference import MOST
 from ksched.objects import (Arena, Container, LabelSelector, Node, NodeSelectorRequirement, NodeSelectorTerm, Pod,
-                            PreferredSchedulingTerm, Taint, Toleration, TopologySpreadConstraint, nodes_array,
-                            pods_array)
+                            PodAffinityTerm, PreferredSchedulingTerm, Taint, Toleration, TopologySpreadConstraint,
+                            nodes_array, pods_array)
+from rtcr_reference import RTCR, SHAPES as FIT_SHAPES
 
 Gi, Mi = 1 << 30, 1 << 20
 GPU = "amd.com/gpu"
@@ -140,5 +142,108 @@ def reference_run(n):
     dumps = [o.plugin_scores(pods_array([p], a)[0]) for p in probes(n)]
     out = {"res": res, "states": o.states(), "used": [o.used_ports(s) for s in range(n)], "placed": list(o.placed),
            "dumps": dumps, "ports": [bool(p.host_ports) for p in ps]}
+    o.close()
+    return out
+
+
+def two_rank_case(cfg):
+    """The mixed stream as a two-rank case (tests/chain_multirank_main.py): the one-pod chain runs replicated,
+    so every rank keeps its own dictionary and used-ports column and applies every commit."""
+    n = cfg["n"]
+    ref = reference_run(n)
+    ns, ps = stream(SEEDS[n], n)
+    a = Arena()
+    na, k = nodes_array(ns, a)
+    sl = u32(range(k))
+    half = len(ps) // 2
+
+    def check(s):
+        if [sorted(s.node_used_ports(slot)) for slot in range(n)] != ref["used"]:
+            return "used ports differ from the reference's mirror"
+
+    return dict(capacity=n, pods_per_round=64, setup=lambda s: s.upsert_nodes_raw(na, sl, k), arena=a,
+                batches=[pods_array(ps[:half], a), pods_array(ps[half:], a)], want=ref["res"], states=ref["states"],
+                check=check, report={"port_fails": int(ref["res"]["_pad"].sum())})
+
+
+# ------------------------------------------------- the chain's launch contexts
+def context(strategy=None, gpu=0, balanced=None):
+    """(PortsReference's keywords, Scheduler's) of a context: MostAllocated or a RequestedToCapacityRatio
+    shape by name, amd.com/gpu listed in the strategy at weight `gpu`, a balanced list."""
+    ref, cfg = {}, {}
+    if strategy == MOST:
+        ref["strategy"], cfg["fit_strategy"] = (MOST, 1, 1), MOST
+    elif strategy:
+        ref["strategy"] = (FIT_SHAPES[strategy], 1, 1)
+        cfg.update(fit_strategy=RTCR, fit_shape=list(FIT_SHAPES[strategy]))
+    if gpu:
+        ref["extended"], cfg["fit_resource_weights"] = {GPU: gpu}, {"cpu": 1, "memory": 1, GPU: gpu}
+    if balanced:
+        ref["balanced"], cfg["balanced_resources"] = list(balanced), list(balanced)
+    return ref, cfg
+
+
+# The ten contexts the chain's launch tells apart for a pod that requests amd.com/gpu: the default strategy,
+# MostAllocated and RequestedToCapacityRatio (the kernels' GF 0 / 1 / 2), the latter two with and without
+# the resource in the strategy (XF), each of the five with and without a balanced list that names it (BAL)
+CONTEXTS = {
+    "most": context(MOST),
+    "most-gpu3": context(MOST, 3),
+    "rtcr-binpack": context("binpack"),
+    "balanced-gpu": context(balanced=["cpu", "memory", GPU]),
+    "rtcr-gpu2-balanced": context("peaked", 2, [GPU, "cpu", "memory"]),
+    "default": context(),
+    "most-balanced": context(MOST, balanced=["cpu", "memory", GPU]),
+    "most-gpu3-balanced": context(MOST, 3, [GPU, "cpu", "memory"]),
+    "rtcr-binpack-balanced": context("binpack", balanced=["cpu", GPU, "memory"]),
+    "rtcr-gpu2": context("peaked", 2),
+}
+
+# The chain-variant pods (tests/test_gpu_chain_variants.py): four kinds, with or without a host port and
+# with or without a required anti-affinity term on kubernetes.io/hostname against their own app label.
+# Each requests one amd.com/gpu, so it takes the one-pod chain under every context
+KINDS = [(ports, anti) for ports in (False, True) for anti in (False, True)]
+# the seed of the 16 extra pods at which, under every context, PortsReference alone schedules a pod of each
+# kind and fails a pod with NodePorts (tests/test_chain_variants_reference.py asserts it)
+EXTRA_SEED = 1
+
+
+def variant_pod(rng, name, ports, anti):
+    app = rng.choice(["web", "api"])
+    p = Pod(name, labels={"app": app}, containers=[Container({"cpu": rng.choice([100, 250]), "memory": 128 * Mi, GPU: 1})])
+    if ports:
+        p.host_ports = [host_port(rng)]
+    if anti:
+        p.affinity_terms = [PodAffinityTerm("kubernetes.io/hostname", LabelSelector({"app": app}), kind="anti-affinity")]
+    return p
+
+
+def variant_pods(seed, j0, per_kind):
+    """per_kind pods of each kind, interleaved."""
+    rng = random.Random(seed)
+    return [variant_pod(rng, f"v{j0 + j}", *KINDS[j % 4]) for j in range(4 * per_kind)]
+
+
+@functools.lru_cache(maxsize=None)
+def variants_reference(name, seed=EXTRA_SEED):
+    """The 65-node mixed stream and then 4 chain-variant pods of each kind through PortsReference alone
+    under the context `name`, computed once per process: the pods, every result, every node's state and
+    used ports, and the dumps of one probe pod of each kind at the end state."""
+    from helpers import res_array
+    from ports_reference import PortsReference
+
+    n = 65
+    ns, ps = stream(SEEDS[n], n)
+    ps = ps + variant_pods(seed, 80_000, 4)
+    probes = variant_pods(2000 + seed, 95_000, 1)
+    a = Arena()
+    o = PortsReference(n, PAIRS, IPS, **CONTEXTS[name][0])
+    na, k = nodes_array(ns, a)
+    o.upsert(na, u32(range(k)), k)
+    pa, m = pods_array(ps, a)
+    res = res_array(o.schedule(pa, m), m)
+    out = {"nodes": ns, "pods": ps, "probes": probes, "res": res, "states": o.states(),
+           "used": [o.used_ports(s) for s in range(n)],
+           "dumps": [o.plugin_scores(pods_array([p], a)[0]) for p in probes]}
     o.close()
     return out

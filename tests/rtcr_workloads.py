@@ -66,6 +66,11 @@ def hetero_reference(kind_name, name):
     return out
 
 
+def two_rank_case(cfg):
+    return W.hetero_case(W.hetero_stream(cfg["kind_name"]), *hetero_reference(cfg["kind_name"], cfg["name"]),
+                         lambda s: use(s, cfg["name"]))
+
+
 @functools.lru_cache(maxsize=None)
 def wide_reference(name):
     from test_gpu_geometry import CAP_B, wide_workload

@@ -84,8 +84,8 @@ def test_virtual_shards(kind_name, strategy_name):
 def test_two_ranks(kind_name, strategy_name):
     # a two-rank in-process world (tests/test_gpu_multirank.py): each rank sweeps its shard, both set the strategy
     env = dict(os.environ, GPU_MAX_HW_QUEUES="16")
-    cfg = {"kind_name": kind_name, "strategy_name": strategy_name}
-    p = subprocess.run([sys.executable, os.path.join(HERE, "fit_multirank_main.py"), json.dumps(cfg)],
+    cfg = {"family": "fit", "kind_name": kind_name, "strategy_name": strategy_name}
+    p = subprocess.run([sys.executable, os.path.join(HERE, "chain_multirank_main.py"), json.dumps(cfg)],
                        capture_output=True, text=True, timeout=120, env=env)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and lines, f"rc={p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-3000:]}"

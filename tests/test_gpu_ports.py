@@ -21,12 +21,11 @@ import numpy as np
 import pytest
 
 import ports_workloads as W
-from fit_reference import MOST, scores_np
+from fit_reference import scores_np
 from helpers import res_array, states_np
 from ksched import Scheduler, _abi
 from ksched.objects import Arena, Container, Node, Pod, nodes_array, pods_array
 from ports_reference import PortsReference
-from rtcr_reference import RTCR, SHAPES
 from test_gpu_spread import Pair
 
 pytestmark = pytest.mark.gpu
@@ -137,7 +136,8 @@ def test_virtual_shards():
 
 def test_two_ranks():
     env = dict(os.environ, GPU_MAX_HW_QUEUES="16")
-    p = subprocess.run([sys.executable, os.path.join(HERE, "ports_multirank_main.py"), json.dumps({"n": 65})],
+    cfg = {"family": "ports", "n": 65}
+    p = subprocess.run([sys.executable, os.path.join(HERE, "chain_multirank_main.py"), json.dumps(cfg)],
                        capture_output=True, text=True, timeout=120, env=env)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and lines, f"rc={p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-3000:]}"
@@ -146,20 +146,10 @@ def test_two_ranks():
     assert res["scheduled"] > 0 and res["port_fails"] > 0
 
 
-# the other NodeResourcesFit strategies once each (one of them with a listed extended resource, which a third
-# of the pods with ports request), and a balanced list that names the GPU: the PORTS instances under GF / XF / BAL
-@pytest.mark.parametrize("name,ref,cfg", [
-    ("most", {"strategy": (MOST, 1, 1)}, {"fit_strategy": MOST}),
-    ("most-gpu3", {"strategy": (MOST, 1, 1), "extended": {W.GPU: 3}},
-     {"fit_strategy": MOST, "fit_resource_weights": {"cpu": 1, "memory": 1, W.GPU: 3}}),
-    ("rtcr-binpack", {"strategy": (SHAPES["binpack"], 1, 1)},
-     {"fit_strategy": RTCR, "fit_shape": list(SHAPES["binpack"])}),
-    ("balanced-gpu", {"balanced": ["cpu", "memory", W.GPU]}, {"balanced_resources": ["cpu", "memory", W.GPU]}),
-    ("rtcr-gpu2-balanced", {"strategy": (SHAPES["peaked"], 1, 1), "extended": {W.GPU: 2},
-                            "balanced": [W.GPU, "cpu", "memory"]},
-     {"fit_strategy": RTCR, "fit_shape": list(SHAPES["peaked"]),
-      "fit_resource_weights": {"cpu": 1, "memory": 1, W.GPU: 2}, "balanced_resources": [W.GPU, "cpu", "memory"]}),
-])
+# every context the chain's launch tells apart (ports_workloads.CONTEXTS): the NodeResourcesFit strategies with
+# and without a listed extended resource, which a third of the pods with ports request, each with and without a
+# balanced list that names the GPU: the PORTS instances under GF / XF / BAL
+@pytest.mark.parametrize("name,ref,cfg", [(name, ref, cfg) for name, (ref, cfg) in W.CONTEXTS.items()])
 def test_context_variants(name, ref, cfg):
     n = 65
     ns, ps = W.stream(W.SEEDS[n], n)

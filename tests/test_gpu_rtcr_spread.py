@@ -72,8 +72,8 @@ def test_virtual_shards(kind_name, name):
 def test_two_ranks(kind_name, name):
     # a two-rank in-process world (tests/test_gpu_multirank.py): each rank sweeps its shard, both set the shape
     env = dict(os.environ, GPU_MAX_HW_QUEUES="16")
-    cfg = {"kind_name": kind_name, "name": name}
-    p = subprocess.run([sys.executable, os.path.join(HERE, "rtcr_multirank_main.py"), json.dumps(cfg)],
+    cfg = {"family": "rtcr", "kind_name": kind_name, "name": name}
+    p = subprocess.run([sys.executable, os.path.join(HERE, "chain_multirank_main.py"), json.dumps(cfg)],
                        capture_output=True, text=True, timeout=120, env=env)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and lines, f"rc={p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-3000:]}"

@@ -179,7 +179,8 @@ def test_virtual_shards(case):
 def test_two_ranks(case):
     # a two-rank in-process world (tests/test_gpu_multirank.py): the chain runs replicated, both ranks set the list
     env = dict(os.environ, GPU_MAX_HW_QUEUES="16")
-    p = subprocess.run([sys.executable, os.path.join(HERE, "xfit_multirank_main.py"), json.dumps({"case": case})],
+    cfg = {"family": "xfit", "case": case}
+    p = subprocess.run([sys.executable, os.path.join(HERE, "chain_multirank_main.py"), json.dumps(cfg)],
                        capture_output=True, text=True, timeout=120, env=env)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and lines, f"rc={p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-3000:]}"

@@ -5,12 +5,16 @@ and the GPU tests (tests/test_gpu_xfit.py).  A stream is driven through a pair
 object with the interface of tests/test_gpu_spread.py Pair (upsert / delete /
 add / schedule / dump_equal / states_equal), as fit_workloads.chain_stream is.
 """
+import ctypes as C
 import random
 
+import numpy as np
+
 from fit_reference import LEAST, MOST
-from ksched.objects import Container, Pod
+from helpers import res_array
+from ksched.objects import Arena, Container, Pod, nodes_array, pods_array
 from rtcr_reference import SHAPES
-from xfit_reference import GPU, HUGE, NIC
+from xfit_reference import GPU, HUGE, NIC, XfitReference
 
 Gi, Mi = 1 << 30, 1 << 20
 
@@ -129,6 +133,41 @@ def sweep_stream(x, seed, size, dumps=True):
             x.dump_equal(xfit_pod(rng, 90_001 + 10 * b), f"sweep seed {seed} {size}: dump of a spread pod, bypass {b}")
     x.dump_equal(xfit_pod(rng, 95_000), f"sweep seed {seed} {size}: dump of a plain pod")
     return pods, res
+
+
+def replicated_case(seed, make_ref, configure):
+    """A two-rank case (tests/chain_multirank_main.py) at the small size: prefilled nodes, then two batches of
+    the mixed stream, which the chain runs replicated.  make_ref(capacity) is the case's reference,
+    configure(scheduler) sets its strategy and lists on a rank."""
+    n, cap = SIZES["small"]
+    rng = random.Random(seed)
+    a = Arena()
+    slots = spread_slots(n, cap)
+    na, k = nodes_array(xfit_nodes(rng, n), a)
+    sl = (C.c_uint32 * k)(*slots)
+    pre = bound_pods(rng, n // 2, 60_000)
+    ba, nb = pods_array(pre, a)
+    bs = (C.c_uint32 * nb)(*[rng.choice(slots) for _ in pre])
+    batches = [pods_array([xfit_pod(rng, b * 1000 + j) for j in range(60)], a) for b in range(2)]
+    ref = make_ref(cap)
+    ref.upsert(na, sl, k)
+    ref.add_pods(ba, bs, nb)
+    want = np.concatenate([res_array(ref.schedule(pa, m), m) for pa, m in batches])
+    states = ref.states()
+    ref.close()
+
+    def setup(s):
+        configure(s)
+        s.upsert_nodes_raw(na, sl, k)
+        assert s.lib.ks_pods_add(s.ctx, ba, bs, nb) == 0
+
+    return dict(capacity=cap, pods_per_round=64, setup=setup, batches=batches, want=want, states=states, arena=a)
+
+
+def two_rank_case(cfg):
+    strategy, extended = CASES[cfg["case"]]
+    return replicated_case(91, lambda cap: XfitReference(cap, strategy, extended),
+                           lambda s: set_strategy(s, strategy, extended))
 
 
 def requests_extended(pod, names):
