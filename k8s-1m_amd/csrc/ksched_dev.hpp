@@ -59,7 +59,7 @@ struct Shard {
   uint32_t base;        // first position
 };
 
-__host__ __device__ inline uint32_t shard_pos(const Shard &s, uint32_t npl, uint32_t l) {
+KS_HD inline uint32_t shard_pos(const Shard &s, uint32_t npl, uint32_t l) {
   const uint32_t w = l % s.waves;
   const uint32_t t = (l / s.waves) % WAVE;
   const uint32_t j = l / (s.waves * WAVE);
@@ -121,7 +121,7 @@ static_assert(sizeof(PodDev) == 128, "PodDev layout");
 // The PreFilterResult program (PF_PREFILTER) is a plain list of slots.
 constexpr int TERM_HDR_WORDS = 1 + 2 * LW;
 enum TermOp : uint32_t { TO_GT = 0, TO_LT = 1, TO_NAME_IN = 0, TO_NAME_NOT_IN = 1 };
-__host__ __device__ inline uint32_t term_words(uint64_t w0) {
+KS_HD inline uint32_t term_words(uint64_t w0) {
   const uint32_t ng = (uint32_t)w0 & 0xFF, nn = ((uint32_t)w0 >> 8) & 0xFF, nm = ((uint32_t)w0 >> 16) & 0xFF;
   return TERM_HDR_WORDS + ng * LW + 2 * (nn + nm);
 }
@@ -250,6 +250,45 @@ struct alignas(16) BlockRec {
 };
 static_assert(sizeof(BlockRec) == 80, "BlockRec layout");
 
+// ------------------------------------------------------------- wave lists
+// The sweep's list of one wave and pod, from the lanes' two best 32-bit keys
+// (b1 >= b2; keys are unique within a wave unless 0): B is the largest b2,
+// t1 >= t2 >= t3 the three largest b1 (0 where fewer); the list holds t1 and
+// t2 where above B, its bound is max(B, t3).  The resource-only sweep folds
+// the lanes' pairs of WL_T pods at once, a lane taking WL_SEG lanes' pairs of
+// one pod (wl_fold) and the segments' tuples meeting by wl_merge; plain C++,
+// checked against the sequential definition by tools/wavelist_check.cpp.
+constexpr int WL_T = 8;                // pods per batch
+constexpr int WL_SEG = WAVE / WL_T;    // lanes' pairs folded by one lane
+constexpr int WL_ROW = WAVE + 1;       // staging row of a pod in 8-byte pairs: the odd stride keeps
+                                       // the transposed 8-byte reads on distinct LDS banks
+struct WaveTuple {
+  uint32_t t1, t2, t3, B;
+};
+KS_HD inline uint32_t wl_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
+KS_HD inline uint32_t wl_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
+KS_HD inline void wl_fold(WaveTuple &w, uint32_t b1, uint32_t b2) {
+  w.t3 = wl_max(w.t3, wl_min(w.t2, b1));
+  w.t2 = wl_max(w.t2, wl_min(w.t1, b1));
+  w.t1 = wl_max(w.t1, b1);
+  w.B = wl_max(w.B, b2);
+}
+// the tuple of the union of two disjoint lane sets
+KS_HD inline WaveTuple wl_merge(const WaveTuple &x, const WaveTuple &y) {
+  WaveTuple r;
+  r.t1 = wl_max(x.t1, y.t1);
+  r.t2 = wl_max(wl_min(x.t1, y.t1), wl_max(x.t2, y.t2));
+  r.t3 = wl_max(wl_max(wl_min(x.t1, y.t2), wl_min(x.t2, y.t1)), wl_max(x.t3, y.t3));
+  r.B = wl_max(x.B, y.B);
+  return r;
+}
+// list entry e of the tuple: 0, 1 the keys (0 = none), 2 the bound
+KS_HD inline uint32_t wl_entry(const WaveTuple &w, uint32_t e) {
+  if (e == 2) return wl_max(w.B, w.t3);
+  const uint32_t t = e == 0 ? w.t1 : w.t2;
+  return t > w.B ? t : 0u;
+}
+
 // Per pod of a round after the merge (max over blocks and shards, then RCCL
 // all-reduce(max) across ranks): the measured normalising maxima and whether
 // any node is feasible.  norm_check turns it into norm_max and the fix flags.
@@ -270,7 +309,7 @@ struct alignas(16) ShardRecHdr {
 };
 static_assert(sizeof(ShardRecHdr) == 48, "ShardRecHdr layout");
 constexpr uint32_t REC_HDR_WORDS = 6;
-__host__ __device__ inline uint32_t rec_words(uint32_t k) { return REC_HDR_WORDS + k; }
+KS_HD inline uint32_t rec_words(uint32_t k) { return REC_HDR_WORDS + k; }
 
 // S0 row of a listed candidate, gathered next to its key after the merge, in
 // the form the resolve computes in: every resource quantity is an integer

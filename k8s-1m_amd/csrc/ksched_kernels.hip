@@ -193,6 +193,8 @@ void sweep_kernel(RoundArgs a) {
   // per pod and wave: feasible, first failures per plugin, #at max (tt, na), max raw (tt, na)
   constexpr int NCNT = NFILT + 5;
   __shared__ uint32_t s_cnt[MAX_PG][NW][NCNT];
+  // resource-only: the lanes' (b1, b2) of a batch of WL_T pods, private to a wave
+  __shared__ uint64_t s_stage[EXT ? 1 : NW][EXT ? 1 : WL_T][EXT ? 1 : WL_ROW];
 
   const uint32_t start = uniform_u32(*a.sstart);
   const uint32_t sh = blockIdx.z;
@@ -249,10 +251,12 @@ void sweep_kernel(RoundArgs a) {
     static_for<NPL>([&](auto J) { kc[J] = (cplus << KEY32_POS_BITS) + (kpos0 - (uint32_t)J * WAVE); });
   }
 
-  for (uint32_t it = p0; it < p1; ++it) {
+  uint32_t feas_v = 0;  // resource-only: lane q holds the feasible nodes of the batch's pod q
+  // One pod (q: its place in the batch, resource-only kernels)
+  auto sweep_pod = [&](const uint32_t it, const uint32_t q) __attribute__((always_inline)) {
     // FIX mode: slice entry it - start of the compacted flagged-pod list
     const uint32_t r = fix ? uniform_u32(a.fix_list[it - start]) : dedup ? uniform_u32(a.ulist[it - start]) : it - start;
-    if (fix && r == FIX_NONE) continue;
+    if (fix && r == FIX_NONE) return;
     const uint32_t pi = start + r;
     const PodDev p = load_pod<!EXT>(a.pods, pi);
     uint32_t tt_max = 0, na_max = 0;
@@ -384,6 +388,12 @@ void sweep_kernel(RoundArgs a) {
       if (p.flags & PF_TT) tmx = (!exceeded && ttc) ? tt_max : wave_max_u32_dpp(tmx);
       if (p.flags & PF_NA) nmx = (!exceeded && nac) ? na_max : wave_max_u32_dpp(nmx);
     }
+    if constexpr (!EXT) {
+      // one 8-byte store per pod; feas rides in lane q of a VGPR (f4 = vcount - feas)
+      s_stage[wid][q][lane] = (uint64_t)b2 << 32 | b1;
+      feas_v = writelane_u32(feas_v, feas, q);
+      return;
+    }
     const uint32_t best = b1, second = b2;
     // Wave list: the lane bests above every lane's second best (top 2) + bound,
     // DPP reductions, skipping those the candidate count makes unnecessary.
@@ -425,6 +435,52 @@ void sweep_kernel(RoundArgs a) {
       s_cnt[pl][wid][7] = nac;
       s_cnt[pl][wid][8] = tmx;
       s_cnt[pl][wid][9] = nmx;
+    }
+  };
+  // The label / taint kernels reduce a pod's wave list at once.  The
+  // resource-only kernels take the pods in batches of WL_T: they set the
+  // lanes' two best keys aside per pod and reduce a batch's lists together.
+  if constexpr (EXT) {
+    for (uint32_t it = p0; it < p1; ++it) sweep_pod(it, 0u);
+  } else {
+    const uint32_t bq = lane % WL_T, bg = lane / WL_T;  // the batch step's pod and lane segment of this lane
+    for (uint32_t b0 = p0; b0 < p1; b0 += WL_T) {
+      const uint32_t nb = min((uint32_t)WL_T, p1 - b0);
+#pragma nounroll
+      for (uint32_t q = 0; q < nb; ++q) sweep_pod(b0 + q, q);
+      // Batch step: lane L takes pod L % WL_T and the pairs of lanes
+      // [WL_SEG (L / WL_T), + WL_SEG), folds them with per-lane min / max, and
+      // the WL_T segments of a pod (lanes WL_T apart) meet in three exchanges.
+      // The staging rows are the wave's own: its LDS accesses complete in order,
+      // so only the compiler has to be kept from moving them across each other.
+      wave_lds_order();
+      WaveTuple w = {0u, 0u, 0u, 0u};
+      static_for<WL_SEG>([&](auto I) {
+        const uint64_t v = s_stage[wid][bq][bg * WL_SEG + (uint32_t)I];
+        wl_fold(w, (uint32_t)v, (uint32_t)(v >> 32));
+      });
+      wave_lds_order();
+      w = wl_merge(w, tuple_ror8(w));
+      w = wl_merge(w, tuple_xor(w, 16));
+      w = wl_merge(w, tuple_xor(w, 32));
+      // lanes 0..2 of a pod's segments widen and store its list entries, back to
+      // packed keys ((score + 1) << 32 | ~slot); segment 0 stores its counters,
+      // the others the words that are zero for a resource-only pod
+      const uint32_t pl = b0 - p0 + bq;
+      if (bq < nb) {
+        if (bg < 3) {
+          const uint32_t k = wl_entry(w, bg);
+          const uint32_t kq = KEY32_POS_MASK - (k & KEY32_POS_MASK);
+          const uint32_t slot = s.lo + (j0 + kq / WAVE) * WAVE * s.waves + (kq % WAVE) * s.waves + lwave;
+          s_keys[pl][wid][bg] = k ? ((uint64_t)(k >> KEY32_POS_BITS) << 32) | (uint64_t)(0xFFFFFFFFu - slot) : 0ull;
+        }
+        static_assert(NCNT == 10 && WL_T == 8, "counter words over the segments");
+        s_cnt[pl][wid][bg < 5 ? bg : bg + 1] = bg == 0 ? feas_v : 0u;  // words 0..4, 6..8
+        if (bg == 0) {
+          s_cnt[pl][wid][5] = vcount - feas_v;
+          s_cnt[pl][wid][9] = 0u;
+        }
+      }
     }
   }
   __syncthreads();

@@ -112,6 +112,36 @@ __device__ __forceinline__ uint32_t wave_max_u32_dpp(uint32_t v) {
   return smax_u32(smax_u32((uint32_t)__builtin_amdgcn_readlane((int)v, 0), (uint32_t)__builtin_amdgcn_readlane((int)v, 16)),
                   smax_u32((uint32_t)__builtin_amdgcn_readlane((int)v, 32), (uint32_t)__builtin_amdgcn_readlane((int)v, 48)));
 }
+// v with lane l's value replaced by the wave-uniform x (l wave-uniform, < 64)
+__device__ __forceinline__ uint32_t writelane_u32(uint32_t v, uint32_t x, uint32_t l) {
+  // two SGPR operands exceed the constant bus, so the lane select goes
+  // through m0.  m0 is reserved: the compiler sets it right before the
+  // instructions that read it (LDS-DMA, s_movrel) and, with it on the clobber
+  // list, orders those around this statement; it warns that it will not
+  // preserve a value across it, and keeps none there
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+  asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(v) : "s"(x), "s"(l) : "m0");
+#pragma clang diagnostic pop
+  return v;
+}
+// A wave's hand-off to itself through LDS (lanes read what other lanes of the
+// wave wrote): the hardware completes one wave's LDS accesses in order, the
+// fences keep the compiler from moving them across this point.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// A wave-list tuple (ksched_dev.hpp) of the lane 8 further round the 16-lane
+// row (DPP row_ror:8 = 0x128), and of lane ^ m for m = 16, 32 (ds_bpermute)
+__device__ __forceinline__ WaveTuple tuple_ror8(const WaveTuple &w) {
+  return {dpp32<0x128>(w.t1), dpp32<0x128>(w.t2), dpp32<0x128>(w.t3), dpp32<0x128>(w.B)};
+}
+__device__ __forceinline__ WaveTuple tuple_xor(const WaveTuple &w, int m) {
+  return {(uint32_t)__shfl_xor((int)w.t1, m, WAVE), (uint32_t)__shfl_xor((int)w.t2, m, WAVE),
+          (uint32_t)__shfl_xor((int)w.t3, m, WAVE), (uint32_t)__shfl_xor((int)w.B, m, WAVE)};
+}
 __device__ __forceinline__ uint32_t min8_u32(uint32_t v) {
   v = min(v, dpp32<0xB1>(v));
   v = min(v, dpp32<0x4E>(v));

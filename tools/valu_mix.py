@@ -8,7 +8,13 @@ for ITS instruction mix, not a constant per instruction.  This tool:
      disassembles it with llvm-objdump;
   2. for every sweep_kernel<NPL, EXT, LWU> instance takes its per-pod loop
      (the longest backward branch: the loop over the pods of a sweep block,
-     nested clause loops counted once) and histograms its VALU opcodes;
+     nested clause loops counted once) and histograms its VALU opcodes.  The
+     resource-only kernels take the pods in batches of WL_T (ksched_dev.hpp):
+     their longest backward branch is the loop over the batches, the longest
+     one inside it the pod loop, and what the outer loop holds besides is the
+     batch step, which runs once per WL_T pods.  loop_valu is VALU per pod
+     there: the pod loop's body (pod_valu) + the batch step's (batch_valu) /
+     WL_T, and the costs are weighted alike;
   3. prices each opcode with the issue cost measured on MI355X at 4 waves per
      SIMD by tools/valu_issue.hip (profiles/valu_issue.jsonl); an opcode the
      microbenchmark does not cover takes its class's median (VOP1/VOP2
@@ -101,10 +107,18 @@ def kernels(lines):
     return out
 
 
-def pod_loop(ins):
-    """[lo, hi) of the longest backward branch's loop."""
+def batch_pods() -> int:
+    """WL_T of ksched_dev.hpp: the pods of one batch step."""
+    m = re.search(r"constexpr int WL_T = (\d+);", (CSRC / "ksched_dev.hpp").read_text())
+    return int(m.group(1))
+
+
+def pod_loop(ins, within=None):
+    """[lo, hi) of the longest backward branch's loop (within: strictly inside that range)."""
     best = None
     for a, op, args in ins:
+        if within and not (within[0] <= a < within[1]):
+            continue
         if not (op.startswith("s_cbranch") or op == "s_branch"):
             continue
         m = re.match(r"^(-?\d+)", args)
@@ -116,6 +130,8 @@ def pod_loop(ins):
         if off >= 0:
             continue
         t = a + 4 + 4 * off
+        if within and (t <= within[0] or a + 4 >= within[1]):
+            continue
         if best is None or a - t > best[1] - best[0]:
             best = (t, a + 4)
     return best
@@ -159,24 +175,37 @@ def main():
     fast_med, slow_med = fast[len(fast) // 2], slow[len(slow) // 2]
     res = {"kernel_src": kernel_src_hash(), "waves_per_simd": WAVES, "source": "profiles/valu_issue.jsonl",
            "class_median": {"fast_32bit": fast_med, "other": slow_med}, "kernels": {}}
+    T = batch_pods()
     for name, ins in kernels(disassemble()).items():
         lo, hi = pod_loop(ins)
-        loop = [(op, args) for a, op, args in ins if lo <= a < hi and op.startswith("v_")]
-        hist = collections.Counter(op for op, _ in loop)
-        n = len(loop)
+        targs = template_args(name)
+        batched = ", false," in targs
+        inner = pod_loop(ins, (lo, hi)) if batched else None
+        if batched and inner is None:
+            raise RuntimeError(f"{targs}: no pod loop inside the loop over the batches")
+        # (opcode, operands, weight): the batch step's instructions run once per T pods
+        loop = [(op, args, 1.0 if not batched or inner[0] <= a < inner[1] else 1.0 / T)
+                for a, op, args in ins if lo <= a < hi and op.startswith("v_")]
+        hist = collections.Counter(op for op, _, w in loop if w == 1.0)
+        bhist = collections.Counter(op for op, _, w in loop if w != 1.0)
+        n = sum(w for _, _, w in loop)
         cyc = covered = 0.0
-        for op, args in loop:
+        for op, args, w in loop:
             v, ok = cost_of(op, costs, fast_med, slow_med, args)
-            cyc += v
-            covered += 1 if ok else 0
-        res["kernels"][template_args(name)] = {
-            "mangled": name, "loop_valu": n, "cycles_per_valu": round(cyc / n, 4),
-            "measured_share": round(covered / n, 4),
-            "hist": dict(hist.most_common())}
+            cyc += v * w
+            covered += w if ok else 0
+        k = {"mangled": name, "loop_valu": round(n, 2) if batched else int(n),"cycles_per_valu": round(cyc / n, 4),
+             "measured_share": round(covered / n, 4),
+             "hist": dict(hist.most_common())}
+        if batched:
+            k.update(pod_valu=sum(hist.values()), batch_valu=sum(bhist.values()), batch_pods=T,
+                     batch_hist=dict(bhist.most_common()))
+        res["kernels"][targs] = k
     out = ROOT / "profiles" / "valu_mix.json"
     out.write_text(json.dumps(res, indent=1) + "\n")
     for k, v in sorted(res["kernels"].items()):
-        print(f"sweep_kernel{k}: {v['loop_valu']} VALU in the pod loop, {v['cycles_per_valu']} cycles each "
+        parts = f" = {v['pod_valu']} + {v['batch_valu']} / {v['batch_pods']}" if "pod_valu" in v else ""
+        print(f"sweep_kernel{k}: {v['loop_valu']}{parts} VALU per pod in the pod loop, {v['cycles_per_valu']} cycles each "
               f"(measured opcodes {v['measured_share']:.0%})")
     print("->", out.relative_to(ROOT))
 
