@@ -29,6 +29,7 @@
 #ifndef KSCHED_H
 #define KSCHED_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -865,6 +866,60 @@ ks_status ks_get_fit_resources(ks_ctx *ctx, ks_fit_resource *out, uint32_t cap, 
  * is below it. */
 ks_status ks_set_balanced_resources(ks_ctx *ctx, const char *const *names, uint32_t n);
 ks_status ks_get_balanced_resources(ks_ctx *ctx, const char **out, uint32_t cap, uint32_t *n);
+
+/* ------------------------------------------------ FitError */
+/* Why a pod has no node: upstream's FitError is a histogram over the reasons
+ * of every node's status ("0/5000 nodes are available: 12 Insufficient memory,
+ * 3 node(s) had untolerated taint {dedicated: infra}, 4985 Insufficient cpu.").
+ * ks_diagnose counts, for one pod against the cache as it is, the nodes
+ * carrying each reason.  A node's reasons are those of its first failing
+ * plugin: one reason, except under NodeResourcesFit, which reports every
+ * insufficient resource and "Too many pods" together -- so a plugin's reason
+ * counts sum to at least plugin_nodes[plugin], and to exactly that for every
+ * plugin but NodeResourcesFit.  A tainted node carries its first untolerated
+ * NoSchedule / NoExecute taint in the node's own taint order. */
+typedef struct {
+  uint32_t plugin;      /* KS_PLUGIN_*, KS_STATUS_NODE_PORTS, or KS_FAIL_PREFILTER_RESULT */
+  uint32_t count;       /* nodes whose status carries this reason */
+  const char *reason;   /* upstream's reason string; owned by the context,
+                           valid until the next ks_diagnose or ks_close */
+} ks_reason;
+
+typedef struct {
+  uint32_t num_all_nodes;                       /* present nodes: FitError.NumAllNodes */
+  uint32_t feasible_nodes;
+  uint32_t plugin_nodes[KS_NUM_FAIL_COUNTS];    /* first-failure counts, as ks_result.fail_counts */
+  uint32_t node_ports_nodes;                    /* as ks_result.fail_node_ports */
+  uint32_t n_reasons;
+  const char *prefilter_msg;                    /* Diagnosis.PreFilterMsg, or NULL (owned as the reasons) */
+} ks_diagnosis;
+
+/* One node-parallel pass on the device; a few hundred bytes come back,
+ * whatever the node count (plus one slot per node with several untolerated
+ * taints).  Like ks_plugin_scores the call answers for the cache at the time
+ * of the call, waits for submitted batches, commits nothing and interns
+ * nothing (no host-port triple, no selector class that outlives the call); it
+ * leaves nextStartNodeIndex alone and is always over every present node, also
+ * with percentage_of_nodes_to_score < 100: a FitError arises only after
+ * upstream's loop has visited the whole list.  It works whether or not the pod
+ * has a feasible node.  A pod ks_pods_check refuses is refused with the same
+ * status and error text.  *n reasons (also d->n_reasons) are copied to out
+ * when cap holds them; KS_ERR_INVALID, with *n set, when cap is below it (the
+ * convention of ks_get_fit_resources).  On a multi-rank context each rank
+ * answers from its own replica of the node table, with no exchange. */
+ks_status ks_diagnose(ks_ctx *ctx, const ks_pod *pod, ks_diagnosis *d, ks_reason *out, uint32_t cap, uint32_t *n);
+
+/* FitError.Error() without the PostFilter part; pure host code, needs no
+ * context (as ks_host_ports_conflict): "0/<num_all_nodes> nodes are
+ * available:", then " <prefilter_msg>." when it is set, else the reasons with
+ * equal strings merged, each as "<count> <reason>", sorted bytewise (Go's
+ * sort.Strings: "10 Insufficient cpu" before "2 Insufficient memory"), joined
+ * by ", " behind one space and closed by "."; nothing more without reasons.
+ * *len is the text's length without the terminator; KS_ERR_INVALID, with *len
+ * set, when cap is below *len + 1; KS_ERR_INVALID also for a null len, null
+ * reasons with n > 0, a null reason string or a null buf with cap > 0. */
+ks_status ks_fit_error_message(uint32_t num_all_nodes, const char *prefilter_msg, const ks_reason *reasons, uint32_t n,
+                               char *buf, size_t cap, size_t *len);
 
 #ifdef __cplusplus
 }

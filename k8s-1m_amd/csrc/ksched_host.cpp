@@ -37,6 +37,7 @@
 #include "ksched.h"
 #include "ksched_ba.hpp"
 #include "ksched_dev.hpp"
+#include "ksched_diag.hpp"
 #include "ksched_kernels.hpp"
 #include "ksched_sync.hpp"
 
@@ -510,6 +511,7 @@ struct ks_ctx {
   uint64_t label_resets = 0, taint_rebuilds = 0;  // dictionary capacity reclaims (diagnostics)
   std::unordered_map<uint32_t, std::vector<uint32_t>> key_nodes;  // key id -> slots having it
   bool compile_for_dump = false;    // ks_plugin_scores' compile: host ports are never interned (PORTS_DUMP)
+  bool compile_force_solo = false;  // ks_diagnose's compile: every pod gets a one-pod program
   bool compile_used_names = false;  // set by compile_pod when a pod resolved a node name to a slot
   uint32_t dict_version = 1;   // taint dictionary / node image set (compiled masks and checks)
   // Normaliser guesses (PodDev::tt_guess / na_guess): the distinct (label
@@ -597,6 +599,13 @@ struct ks_ctx {
   int32_t pct = 100;
   uint32_t *d_win = nullptr;
   uint8_t *d_win_st = nullptr;
+  // ks_diagnose: the pass's record and its list of the nodes
+  // with several untolerated taints ([cap] slots), allocated by the first
+  // call; the reason strings and the PreFilter message the last call handed out
+  DiagRec *d_diag_rec = nullptr;
+  uint32_t *d_diag_list = nullptr;
+  std::vector<std::string> diag_strs;
+  std::string diag_prefilter;
   int64_t *d_sraw = nullptr;
   uint64_t *d_spart = nullptr;
   // replica runs: sort keys and positions, group starts, control
@@ -2787,7 +2796,9 @@ ks_status solo_compile(ks_ctx *c, const ks_pod &p, PodDev &d, ProgBuf &cl, bool 
     if ((st = ipa_compile(c, p, create, refs, &aff, &aff_flags))) return st;
   }
   // (percentageOfNodesToScore < 100: every pod takes the chain, which holds the window pass)
-  if (!p.n_spread && xr.empty() && imgs.empty() && aff.empty() && !has_ports && c->pct == 100) return KS_OK;
+  if (!p.n_spread && xr.empty() && imgs.empty() && aff.empty() && !has_ports && c->pct == 100 &&
+      !(create && c->compile_force_solo))
+    return KS_OK;
   // multi-rank contexts run the one-pod path replicated: every rank holds the
   // whole node table and every commit, so each rank's chain over
   // all positions gives the same result with no exchange
@@ -4986,6 +4997,117 @@ ks_status ks_plugin_scores(ks_ctx *c, const ks_pod *pod, ks_node_score *out) {
     out[i] = s;
   }
   return KS_OK;
+}
+
+// FitError's reasons of one pod: the pod compiled as a
+// one-pod-chain pod whatever its flags, [prep + min], the diagnose pass, and
+// the record turned into reason rows with the context's names.
+ks_status ks_diagnose(ks_ctx *c, const ks_pod *pod, ks_diagnosis *dg, ks_reason *out, uint32_t cap, uint32_t *n) {
+  if (!c || !pod || !dg || !n || (cap && !out)) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  PodDev d;
+  ProgBuf cl;
+  ks_status st;
+  uint64_t epoch0;
+  uint32_t num_all;
+  {
+    std::unique_lock<std::mutex> g(c->mu);
+    {  // ks_pods_check's verdict on the pod, with its status and text
+      PodDev d0;
+      ProgBuf cl0;
+      if ((st = compile_batch(c, pod, 1, &d0, cl0, g))) {
+        std::string e;
+        {
+          std::lock_guard<std::mutex> ge(c->err_mu);
+          e = "pod 0: " + c->err;
+        }
+        return c->fail(st, "%s", e.c_str());
+      }
+    }
+    epoch0 = c->class_epoch;
+    c->compile_for_dump = c->compile_force_solo = true;  // no host-port triple interned; a program for every pod
+    st = compile_batch(c, pod, 1, &d, cl, g, true);
+    c->compile_for_dump = c->compile_force_solo = false;
+    if (!st) st = upload_dirty_ext(c, c->xm);
+    if (!st && !c->d_diag_rec && !(st = dalloc(c, &c->d_diag_rec, 1))) st = dalloc(c, &c->d_diag_list, c->cap);
+    num_all = c->n_present;
+  }
+  // selector classes the compile created are dropped again below, whatever happens in between
+  auto drop_classes = [&] {
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int k = 0; k < MAX_CLASSES; ++k) {
+      SpreadClass &sc = c->classes[k];
+      if (!sc.live || sc.born <= epoch0 || sc.refs) continue;
+      c->class_of.erase(sc.canon);
+      sc = SpreadClass();
+    }
+  };
+  DiagRec rec{};
+  std::vector<uint32_t> multi;
+  if (!st) st = [&]() -> ks_status {
+    ks_status s;
+    const size_t bytes = sizeof(PodDev) + cl.w.size() * 8 + sizeof(DiagRec) + 2048;
+    if ((s = xfer_begin(c, bytes, bytes))) return s;
+    PodDev *d_pod = dscratch<PodDev>(c, 1);
+    uint64_t *d_cl = dscratch<uint64_t>(c, cl.w.size());
+    if ((s = h2d(c, d_pod, &d, sizeof d)) || (s = h2d(c, d_cl, cl.w.data(), cl.w.size() * 8))) return s;
+    SpreadArgs sa = spread_args(c);
+    sa.pods = d_pod;
+    sa.clauses = d_cl;
+    sa.pod = 0;
+    sa.no_commit = 1;
+    const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + d.solo_off);
+    sa.ports_conflict = hd->ports;  // (the program holds the conflict mask itself: PORTS_DUMP)
+    const DiagArgs ga{c->d_diag_rec, c->d_diag_list, c->cap};
+    HIPC(c, launch_diagnose(sa, ga, solo_needs(hd).passes, c->stream));
+    if ((s = d2h(c, &rec, c->d_diag_rec, sizeof rec)) || (s = xfer_sync(c))) return s;
+    if (rec.n_multi > c->cap) return c->fail(KS_ERR_DEVICE, "diagnose: %u listed nodes for %u slots", rec.n_multi, c->cap);
+    if (!rec.n_multi) return KS_OK;
+    multi.resize(rec.n_multi);  // the list's used prefix alone
+    if ((s = xfer_begin(c, (size_t)rec.n_multi * 4 + 1024, 0)) ||
+        (s = d2h(c, multi.data(), c->d_diag_list, (size_t)rec.n_multi * 4)) || (s = xfer_sync(c)))
+      return s;
+    return KS_OK;
+  }();
+  drop_classes();
+  if (st) return st;
+  DiagNames nm;
+  std::vector<DiagRow> rows;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    // a node with several untolerated taints reports the first in its own taint order
+    for (uint32_t slot : multi) {
+      if (slot >= c->cap) return c->fail(KS_ERR_DEVICE, "diagnose: listed slot %u >= capacity", slot);
+      for (auto &t : c->nodes[slot].hard_taints) {
+        auto it = c->hard_dict.find(TaintKey{t[0], t[1], (int32_t)t[2]});
+        if (it == c->hard_dict.end() || (d.tol_hard >> it->second & 1ull)) continue;
+        rec.taint[it->second]++;
+        break;
+      }
+    }
+    for (size_t b = 0; b < c->hard_list.size() && b < (size_t)DIAG_TAINT_BINS; ++b)
+      nm.taint[b] = diag_taint_reason(c->strs[c->hard_list[b].key], c->strs[c->hard_list[b].value]);
+    for (size_t x = 0; x < c->xres_names.size() && x < 8; ++x) nm.xres[x] = c->strs[c->xres_names[x]];
+  }
+  const bool conflict = d.flags & PF_NA_CONFLICT;
+  diag_rows(rec, nm, conflict, &rows);
+  std::memset(dg, 0, sizeof *dg);
+  diag_counts(rec, dg);
+  dg->num_all_nodes = num_all;
+  dg->n_reasons = *n = (uint32_t)rows.size();
+  c->diag_strs.clear();
+  for (DiagRow &r : rows) c->diag_strs.push_back(std::move(r.reason));
+  c->diag_prefilter = conflict ? REASON_AFFINITY_CONFLICT : "";
+  dg->prefilter_msg = conflict ? c->diag_prefilter.c_str() : nullptr;
+  if (cap < rows.size()) return c->fail(KS_ERR_INVALID, "diagnose: %zu reasons, room for %u", rows.size(), cap);
+  for (size_t i = 0; i < rows.size(); ++i) out[i] = ks_reason{rows[i].plugin, rows[i].count, c->diag_strs[i].c_str()};
+  return KS_OK;
+}
+
+ks_status ks_fit_error_message(uint32_t num_all_nodes, const char *prefilter_msg, const ks_reason *reasons, uint32_t n,
+                               char *buf, size_t cap, size_t *len) {
+  return fit_error_message(num_all_nodes, prefilter_msg, reasons, n, buf, cap, len);
 }
 
 ks_status ks_node_states(ks_ctx *c, const uint32_t *slots, uint32_t n, ks_node_state *out) {

@@ -240,6 +240,20 @@ struct ReplicaArgs {
 
 hipError_t launch_spread_pod(const SpreadArgs &a, uint32_t passes, hipStream_t st);
 hipError_t launch_spread_reset(const SpreadArgs &a, hipStream_t st);
+// the chain's prep / min passes alone (passes: SPL_PREP / SPL_MIN)
+hipError_t launch_spread_counts(const SpreadArgs &a, uint32_t passes, hipStream_t st);
+// ks_diagnose (ksched_diag.hip): [prep + min], the diagnose
+// pass in the filter pass's place, then the domain scratch and the
+// accumulators cleared as the chain's select / commit leave them.  rec is
+// zeroed first; list [list_cap]: slots of the nodes with several untolerated
+// taints (rec->n_multi of them).
+struct DiagRec;
+struct DiagArgs {
+  DiagRec *rec;
+  uint32_t *list;
+  uint32_t list_cap;
+};
+hipError_t launch_diagnose(const SpreadArgs &a, const DiagArgs &g, uint32_t passes, hipStream_t st);
 // [prep + min passes (passes: SPL_PREP / SPL_MIN, a DoNotSchedule
 // constraint)], the filter pass for a.pod, keys, sort, groups, the run
 // kernel; ctl zeroed first

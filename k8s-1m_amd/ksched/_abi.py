@@ -334,6 +334,16 @@ class KsFitResource(C.Structure):  # ks_fit_resource (ks_set_fit_strategy_resour
     _fields_ = [("name", C.c_char_p), ("weight", C.c_int32), ("_pad", C.c_int32)]
 
 
+class KsReason(C.Structure):  # ks_reason (ks_diagnose / ks_fit_error_message)
+    _fields_ = [("plugin", C.c_uint32), ("count", C.c_uint32), ("reason", C.c_char_p)]
+
+
+class KsDiagnosis(C.Structure):  # ks_diagnosis (ks_diagnose)
+    _fields_ = [("num_all_nodes", C.c_uint32), ("feasible_nodes", C.c_uint32), ("plugin_nodes", C.c_uint32 * 8),
+                ("node_ports_nodes", C.c_uint32), ("n_reasons", C.c_uint32), ("prefilter_msg", C.c_char_p)]
+
+
+DIAG_MAX_REASONS = 96  # more rows than a diagnosis can hold: 63 taints, 11 NodeResourcesFit reasons, 12 others
 FIT_MAX_RESOURCES = 8  # extended resources a strategy may list
 BALANCED_MAX_RESOURCES = 10  # names a balanced list may hold: cpu, memory and 8 scalar resources
 FIT_LEAST_ALLOCATED, FIT_MOST_ALLOCATED, FIT_REQUESTED_TO_CAPACITY_RATIO = 0, 1, 2
@@ -362,6 +372,7 @@ KSCHED_SYMBOLS = [
     "ks_set_fit_strategy_resources", "ks_get_fit_resources",
     "ks_set_balanced_resources", "ks_get_balanced_resources",
     "ks_host_ports_conflict", "ks_node_used_ports",
+    "ks_diagnose", "ks_fit_error_message",
 ]
 KSGATHER_SYMBOLS = [
     "ksg_open", "ksg_close", "ksg_set_members", "ksg_record_and_wait", "ksg_pending", "ksg_fnv1_32", "ksg_target_index",
@@ -446,6 +457,9 @@ def ksched_lib() -> C.CDLL:
     L.ks_get_balanced_resources.argtypes = [vp, P(C.c_char_p), C.c_uint32, P(C.c_uint32)]
     L.ks_host_ports_conflict.argtypes = [P(KsHostPort), P(KsHostPort)]
     L.ks_node_used_ports.argtypes = [vp, C.c_uint32, P(KsHostPort), C.c_uint32, P(C.c_uint32)]
+    L.ks_diagnose.argtypes = [vp, P(KsPod), P(KsDiagnosis), P(KsReason), C.c_uint32, P(C.c_uint32)]
+    L.ks_fit_error_message.argtypes = [C.c_uint32, C.c_char_p, P(KsReason), C.c_uint32, C.c_char_p, C.c_size_t,
+                                       P(C.c_size_t)]
     L.ks_debug_counters.argtypes = [vp, P(C.c_uint64)]
     L.ks_debug_sweep_geometry.argtypes = [vp, C.c_int32, P(C.c_uint64)]
     L.ks_debug_set_profile.argtypes = [vp, C.c_int32]

@@ -74,6 +74,32 @@ class FitError(Exception):  # framework.FitError
         super().__init__(f"0/{num_all_nodes} nodes are available for pod {pod}: {diagnosis.node_to_status}")
 
 
+@dataclass
+class FitDiagnosis:  # what a FitError says: Diagnosis' reasons as a histogram over the nodes (ks_diagnose)
+    num_all_nodes: int
+    feasible_nodes: int
+    plugin_nodes: List[int]      # nodes by first failing plugin (FILTER_PLUGINS, then the PreFilterResult's)
+    node_ports_nodes: int        # ... by NodePorts
+    reasons: Dict[str, int]      # upstream's reason string -> nodes whose status carries it
+    prefilter_msg: Optional[str]
+    message: str                 # FitError.Error() without the PostFilter part
+
+
+def fit_error_message(num_all_nodes: int, reasons, prefilter_msg: Optional[str] = None) -> str:
+    """FitError.Error() of (reason, count) pairs (ks_fit_error_message: pure host code)."""
+    lib = _abi.ksched_lib()
+    pairs = list(reasons.items()) if isinstance(reasons, dict) else list(reasons)
+    arr = (_abi.KsReason * max(1, len(pairs)))(*[_abi.KsReason(0, int(c), str(r).encode()) for r, c in pairs])
+    pm = None if prefilter_msg is None else prefilter_msg.encode()
+    n = C.c_size_t()
+    lib.ks_fit_error_message(num_all_nodes, pm, arr, len(pairs), None, 0, C.byref(n))  # sizes the buffer
+    buf = C.create_string_buffer(n.value + 1)
+    st = lib.ks_fit_error_message(num_all_nodes, pm, arr, len(pairs), buf, n.value + 1, C.byref(n))
+    if st != 0:
+        raise _abi.KschedError(st, "ks_fit_error_message")
+    return buf.value.decode()
+
+
 class FrameworkError(Exception):
     """A plugin returned an Error status (e.g. NodeAffinity PreScore parse error)."""
 
@@ -424,6 +450,25 @@ class Scheduler:
         out = (_abi.KsNodeScore * self.capacity)()
         self._ok(self.lib.ks_plugin_scores(self.ctx, arr, out))
         return list(out)
+
+    def diagnose(self, pod: Pod) -> FitDiagnosis:
+        """Why the pod has no node, as upstream's FitError tells it: the nodes
+        carrying each status reason, counted by one pass on the device against
+        the cache as it is (ks_diagnose).  Nothing is committed; it also
+        answers for a pod that has feasible nodes."""
+        a = Arena()
+        arr, _ = pods_array([pod], a)
+        d = _abi.KsDiagnosis()
+        out = (_abi.KsReason * _abi.DIAG_MAX_REASONS)()
+        n = C.c_uint32()
+        self._ok(self.lib.ks_diagnose(self.ctx, arr, C.byref(d), out, _abi.DIAG_MAX_REASONS, C.byref(n)))
+        rows = [(out[i].reason.decode(), int(out[i].count)) for i in range(n.value)]
+        reasons: Dict[str, int] = {}
+        for r, c in rows:
+            reasons[r] = reasons.get(r, 0) + c
+        pm = d.prefilter_msg.decode() if d.prefilter_msg else None
+        return FitDiagnosis(int(d.num_all_nodes), int(d.feasible_nodes), [int(v) for v in d.plugin_nodes],
+                            int(d.node_ports_nodes), reasons, pm, fit_error_message(int(d.num_all_nodes), rows, pm))
 
     def node_states(self, slots: Sequence[int]) -> List[_abi.KsNodeState]:
         sl = (C.c_uint32 * max(1, len(slots)))(*slots)
