@@ -921,6 +921,55 @@ ks_status ks_diagnose(ks_ctx *ctx, const ks_pod *pod, ks_diagnosis *d, ks_reason
 ks_status ks_fit_error_message(uint32_t num_all_nodes, const char *prefilter_msg, const ks_reason *reasons, uint32_t n,
                                char *buf, size_t cap, size_t *len);
 
+/* --------------------------------------------- NodePluginScores */
+/* Why this node, and what were the alternatives: ks_explain returns, for one
+ * pod against the cache as it is, the k feasible nodes with the highest
+ * TotalScore and their per-plugin scores -- what upstream's scheduler keeps as
+ * NodePluginScores for the nodes it scored -- and the size of selectHost's tie
+ * set.  ks_plugin_scores answers the same question with one record per slot;
+ * ks_explain selects on the device and brings back 24 + 64 k bytes, whatever
+ * the node count. */
+#define KS_EXPLAIN_MAX_CANDIDATES 128
+typedef struct {
+  uint32_t slot;
+  uint32_t _pad;
+  ks_node_score score;   /* field for field ks_plugin_scores' record of the slot (status -1) */
+} ks_candidate;
+
+typedef struct {
+  uint32_t num_all_nodes;    /* present nodes */
+  uint32_t feasible_nodes;
+  uint32_t n_candidates;     /* min(k, feasible_nodes) entries written */
+  uint32_t top_score_nodes;  /* feasible nodes whose total_score equals the best (selectHost's tie set) */
+  int64_t top_score;         /* 0 when no node is feasible */
+} ks_explanation;
+
+/* out[0 .. n_candidates) are the feasible nodes with the highest TotalScore,
+ * ordered by TotalScore descending, then slot ascending -- the order of the
+ * packed key (TotalScore + 1) << 32 | ~slot the scheduling kernels maximise,
+ * so out[0] is the node a following ks_schedule of that pod alone picks on a
+ * context with percentage_of_nodes_to_score 100.  k is in 1 ..
+ * KS_EXPLAIN_MAX_CANDIDATES and out has room for k entries; k 0 or above the
+ * maximum, or a null argument, gives KS_ERR_INVALID.  A pod without a feasible
+ * node gives KS_OK with feasible_nodes, n_candidates, top_score_nodes and
+ * top_score 0: ks_diagnose says why.
+ *
+ * The call shares ks_diagnose's rules.  It answers for the cache at the time
+ * of the call, waits for submitted batches, commits nothing and interns
+ * nothing (no host-port triple, no selector class that outlives the call), and
+ * leaves nextStartNodeIndex alone.  A pod ks_pods_check refuses is refused
+ * with the same status and error text; for any other pod the call returns the
+ * status ks_plugin_scores returns for it (so KS_OK also for a pod whose
+ * PreScore is an Error status, which ks_schedule reports as KS_POD_ERROR).
+ * The fit strategy and the balanced list in force apply as they do to
+ * ks_plugin_scores.  On a multi-rank context each rank answers from its own
+ * replica of the node table, with no exchange.
+ *
+ * With percentage_of_nodes_to_score < 100 the call is still over every
+ * present node, as ks_plugin_scores and ks_diagnose are: a following
+ * ks_schedule then chooses within its window, which need not hold out[0]. */
+ks_status ks_explain(ks_ctx *ctx, const ks_pod *pod, uint32_t k, ks_explanation *e, ks_candidate *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@
 #include "ksched_ba.hpp"
 #include "ksched_dev.hpp"
 #include "ksched_diag.hpp"
+#include "ksched_explain.hpp"
 #include "ksched_kernels.hpp"
 #include "ksched_sync.hpp"
 
@@ -606,6 +607,15 @@ struct ks_ctx {
   uint32_t *d_diag_list = nullptr;
   std::vector<std::string> diag_strs;
   std::string diag_prefilter;
+  // ks_explain: the blocks' key lists and tie pairs, the
+  // final keys and the record, allocated by the first call
+  struct ExplainDev {
+    uint64_t blk_keys[SPREAD_MAX_BLOCKS][KS_EXPLAIN_MAX_CANDIDATES];
+    TopkBest blk_best[SPREAD_MAX_BLOCKS];
+    uint64_t keys[KS_EXPLAIN_MAX_CANDIDATES];
+    ExplainOut out;
+  };
+  ExplainDev *d_explain = nullptr;
   int64_t *d_sraw = nullptr;
   uint64_t *d_spart = nullptr;
   // replica runs: sort keys and positions, group starts, control
@@ -5108,6 +5118,84 @@ ks_status ks_diagnose(ks_ctx *c, const ks_pod *pod, ks_diagnosis *dg, ks_reason 
 ks_status ks_fit_error_message(uint32_t num_all_nodes, const char *prefilter_msg, const ks_reason *reasons, uint32_t n,
                                char *buf, size_t cap, size_t *len) {
   return fit_error_message(num_all_nodes, prefilter_msg, reasons, n, buf, cap, len);
+}
+
+// A pod's best nodes with their per-plugin scores: the pod
+// compiled as a one-pod-chain pod whatever its flags, as ks_diagnose compiles
+// it, the chain's front, and the explain passes in the select pass's place.
+ks_status ks_explain(ks_ctx *c, const ks_pod *pod, uint32_t k, ks_explanation *ex, ks_candidate *out) {
+  if (!c || !pod || !ex || !out || !k || k > KS_EXPLAIN_MAX_CANDIDATES) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  PodDev d;
+  ProgBuf cl;
+  ks_status st;
+  uint64_t epoch0;
+  uint32_t num_all;
+  {
+    std::unique_lock<std::mutex> g(c->mu);
+    {  // ks_pods_check's verdict on the pod, with its status and text
+      PodDev d0;
+      ProgBuf cl0;
+      if ((st = compile_batch(c, pod, 1, &d0, cl0, g))) {
+        std::string e;
+        {
+          std::lock_guard<std::mutex> ge(c->err_mu);
+          e = "pod 0: " + c->err;
+        }
+        return c->fail(st, "%s", e.c_str());
+      }
+    }
+    epoch0 = c->class_epoch;
+    c->compile_for_dump = c->compile_force_solo = true;  // no host-port triple interned; a program for every pod
+    st = compile_batch(c, pod, 1, &d, cl, g, true);
+    c->compile_for_dump = c->compile_force_solo = false;
+    if (!st) st = upload_dirty_ext(c, c->xm);
+    if (!st && !c->d_explain) st = dalloc(c, &c->d_explain, 1);
+    num_all = c->n_present;
+  }
+  ExplainOut got;
+  if (!st) st = [&]() -> ks_status {
+    ks_status s;
+    const size_t back = sizeof(ExplainRec) + (size_t)k * sizeof(ks_candidate);
+    const size_t bytes = sizeof(PodDev) + cl.w.size() * 8 + back + 2048;
+    if ((s = xfer_begin(c, bytes, bytes))) return s;
+    PodDev *d_pod = dscratch<PodDev>(c, 1);
+    uint64_t *d_cl = dscratch<uint64_t>(c, cl.w.size());
+    if ((s = h2d(c, d_pod, &d, sizeof d)) || (s = h2d(c, d_cl, cl.w.data(), cl.w.size() * 8))) return s;
+    SpreadArgs sa = spread_args(c);
+    sa.pods = d_pod;
+    sa.clauses = d_cl;
+    sa.pod = 0;
+    sa.no_commit = 1;
+    sa.nslots = c->cap;
+    const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + d.solo_off);
+    sa.ports_conflict = hd->ports;  // (the program holds the conflict mask itself: PORTS_DUMP)
+    ks_ctx::ExplainDev *dv = c->d_explain;
+    const ExplainArgs xa{&dv->blk_keys[0][0], dv->blk_best, dv->keys, &dv->out, k};
+    HIPC(c, launch_explain(sa, xa, chain_passes(&sa, ba_columns(c), solo_needs(hd)), c->stream));
+    if ((s = d2h(c, &got, &dv->out, back)) || (s = xfer_sync(c))) return s;
+    return KS_OK;
+  }();
+  {  // selector classes the compile created are dropped again, whatever happened in between
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int q = 0; q < MAX_CLASSES; ++q) {
+      SpreadClass &sc = c->classes[q];
+      if (!sc.live || sc.born <= epoch0 || sc.refs) continue;
+      c->class_of.erase(sc.canon);
+      sc = SpreadClass();
+    }
+  }
+  if (st) return st;
+  if (got.rec.n_candidates > k) return c->fail(KS_ERR_DEVICE, "explain: %u candidates for k %u", got.rec.n_candidates, k);
+  std::memset(ex, 0, sizeof *ex);
+  ex->num_all_nodes = num_all;
+  ex->feasible_nodes = got.rec.feasible;
+  ex->n_candidates = got.rec.n_candidates;
+  ex->top_score_nodes = got.rec.top_count;
+  ex->top_score = got.rec.top_score;
+  std::memcpy(out, got.cand, (size_t)got.rec.n_candidates * sizeof(ks_candidate));
+  return KS_OK;
 }
 
 ks_status ks_node_states(ks_ctx *c, const uint32_t *slots, uint32_t n, ks_node_state *out) {

@@ -254,6 +254,27 @@ struct DiagArgs {
   uint32_t list_cap;
 };
 hipError_t launch_diagnose(const SpreadArgs &a, const DiagArgs &g, uint32_t passes, hipStream_t st);
+// the chain's front for a.pod without a window: [prep + min], the filter pass
+// launch_spread_pod would choose for `passes`, [score]; the accumulators and
+// the per-position columns (st, part, raw, ipa_raw) stay as the select pass
+// finds them
+hipError_t launch_spread_front(const SpreadArgs &a, uint32_t passes, hipStream_t st);
+// ks_explain (ksched_explain.hip): the chain's front, the
+// top-k pass in the select pass's place, the one-workgroup merge, the gather
+// of the winners' ks_node_score records, then the accumulators reset.
+// blk_keys [SPREAD_MAX_BLOCKS][KS_EXPLAIN_MAX_CANDIDATES], blk_best
+// [SPREAD_MAX_BLOCKS], keys [KS_EXPLAIN_MAX_CANDIDATES]; a.nslots: the slots
+// of slot_pos.
+struct TopkBest;
+struct ExplainOut;
+struct ExplainArgs {
+  uint64_t *blk_keys;
+  TopkBest *blk_best;
+  uint64_t *keys;
+  ExplainOut *out;
+  uint32_t k;
+};
+hipError_t launch_explain(const SpreadArgs &a, const ExplainArgs &x, uint32_t passes, hipStream_t st);
 // [prep + min passes (passes: SPL_PREP / SPL_MIN, a DoNotSchedule
 // constraint)], the filter pass for a.pod, keys, sort, groups, the run
 // kernel; ctl zeroed first

@@ -1880,6 +1880,26 @@ hipError_t launch_spread_counts(const SpreadArgs &a, uint32_t passes, hipStream_
   return hipGetLastError();
 }
 
+// The chain's front without a window, for passes of another unit that take
+// the select pass's place (ksched_explain.hip): the filter variant is chosen
+// here, as launch_spread_pod chooses it.
+hipError_t launch_spread_front(const SpreadArgs &a, uint32_t passes, hipStream_t st) {
+  if (a.win_mode || a.dump) return hipErrorInvalidValue;
+  const uint32_t blocks =
+      std::max<uint32_t>(1, std::min<uint32_t>((a.npos + SP_THREADS - 1) / SP_THREADS, (uint32_t)SPREAD_MAX_BLOCKS));
+  const bool xf = (passes & SPL_XFIT) && a.fit_general;
+  const bool bal = (passes & SPL_BAL) && (a.bal_lo | a.bal_hi);
+  const bool ports = (passes & SPL_PORTS) && a.used_ports;
+  const uint32_t gf = a.fit_general == 2 ? 2u : a.fit_general ? 1u : 0u;
+  const SpreadKernel filter = kFilterVariants[filter_index(passes & SPL_AFF, gf, xf, bal, ports)];
+  if (!filter) return hipErrorInvalidValue;
+  if (passes & SPL_PREP) spread_prep_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
+  if (passes & SPL_MIN) spread_min_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
+  filter<<<blocks, SP_THREADS, 0, st>>>(a);
+  if (passes & SPL_SCORE) spread_score_kernel<<<blocks, SP_THREADS, 0, st>>>(a);
+  return hipGetLastError();
+}
+
 hipError_t launch_spread_reset(const SpreadArgs &a, hipStream_t st) {
   SpreadArgs z = a;
   z.no_commit = 1;  // reset only: no result, no commit

@@ -9,6 +9,7 @@ from .framework import (  # noqa: F401
     Code,
     CycleState,
     Diagnosis,
+    Explanation,
     FitDiagnosis,
     FitError,
     FrameworkError,

@@ -343,7 +343,17 @@ class KsDiagnosis(C.Structure):  # ks_diagnosis (ks_diagnose)
                 ("node_ports_nodes", C.c_uint32), ("n_reasons", C.c_uint32), ("prefilter_msg", C.c_char_p)]
 
 
-DIAG_MAX_REASONS = 96  # more rows than a diagnosis can hold: 63 taints, 11 NodeResourcesFit reasons, 12 others
+class KsCandidate(C.Structure):  # ks_candidate (ks_explain)
+    _fields_ = [("slot", C.c_uint32), ("_pad", C.c_uint32), ("score", KsNodeScore)]
+
+
+class KsExplanation(C.Structure):  # ks_explanation (ks_explain)
+    _fields_ = [("num_all_nodes", C.c_uint32), ("feasible_nodes", C.c_uint32), ("n_candidates", C.c_uint32),
+                ("top_score_nodes", C.c_uint32), ("top_score", C.c_int64)]
+
+
+EXPLAIN_MAX_CANDIDATES = 128  # KS_EXPLAIN_MAX_CANDIDATES
+DIAG_MAX_REASONS = 96 # more rows than a diagnosis can hold: 63 taints, 11 NodeResourcesFit reasons, 12 others
 FIT_MAX_RESOURCES = 8  # extended resources a strategy may list
 BALANCED_MAX_RESOURCES = 10  # names a balanced list may hold: cpu, memory and 8 scalar resources
 FIT_LEAST_ALLOCATED, FIT_MOST_ALLOCATED, FIT_REQUESTED_TO_CAPACITY_RATIO = 0, 1, 2
@@ -373,6 +383,7 @@ KSCHED_SYMBOLS = [
     "ks_set_balanced_resources", "ks_get_balanced_resources",
     "ks_host_ports_conflict", "ks_node_used_ports",
     "ks_diagnose", "ks_fit_error_message",
+    "ks_explain",
 ]
 KSGATHER_SYMBOLS = [
     "ksg_open", "ksg_close", "ksg_set_members", "ksg_record_and_wait", "ksg_pending", "ksg_fnv1_32", "ksg_target_index",
@@ -458,6 +469,7 @@ def ksched_lib() -> C.CDLL:
     L.ks_host_ports_conflict.argtypes = [P(KsHostPort), P(KsHostPort)]
     L.ks_node_used_ports.argtypes = [vp, C.c_uint32, P(KsHostPort), C.c_uint32, P(C.c_uint32)]
     L.ks_diagnose.argtypes = [vp, P(KsPod), P(KsDiagnosis), P(KsReason), C.c_uint32, P(C.c_uint32)]
+    L.ks_explain.argtypes = [vp, P(KsPod), C.c_uint32, P(KsExplanation), P(KsCandidate)]
     L.ks_fit_error_message.argtypes = [C.c_uint32, C.c_char_p, P(KsReason), C.c_uint32, C.c_char_p, C.c_size_t,
                                        P(C.c_size_t)]
     L.ks_debug_counters.argtypes = [vp, P(C.c_uint64)]

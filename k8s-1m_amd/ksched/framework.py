@@ -115,11 +115,34 @@ class NodePluginScores:  # framework.NodePluginScores
     name: str
     scores: List[PluginScore]
     total_score: int
+    slot: int = -1                             # Scheduler.explain: the node's slot
+    raw: Optional[_abi.KsNodeScore] = None     # ... and its ks_node_score record
 
 
 @dataclass
 class NodePluginScoresState:  # fork-only framework.NodePluginScoresState
     node_plugin_scores: List[NodePluginScores]
+
+
+# The normalised score of each score plugin of DEFAULT_WEIGHTS in a ks_node_score record.
+SCORE_FIELDS = {
+    "NodeResourcesFit": "least_allocated",
+    "NodeResourcesBalancedAllocation": "balanced_allocation",
+    "TaintToleration": "taint_score",
+    "NodeAffinity": "affinity_score",
+    "ImageLocality": "image_locality",
+    "PodTopologySpread": "spread_score",
+    "InterPodAffinity": "affinity_pod_score",
+}
+
+
+@dataclass
+class Explanation:  # a pod's best nodes with their NodePluginScores (ks_explain)
+    num_all_nodes: int
+    feasible_nodes: int
+    top_score: int                 # 0 when no node is feasible
+    top_score_nodes: int           # feasible nodes at top_score: selectHost's tie set
+    candidates: List[NodePluginScores]  # TotalScore descending, then slot ascending
 
 
 class CycleState(dict):  # framework.CycleState (Read / Write)
@@ -469,6 +492,27 @@ class Scheduler:
         pm = d.prefilter_msg.decode() if d.prefilter_msg else None
         return FitDiagnosis(int(d.num_all_nodes), int(d.feasible_nodes), [int(v) for v in d.plugin_nodes],
                             int(d.node_ports_nodes), reasons, pm, fit_error_message(int(d.num_all_nodes), rows, pm))
+
+    def explain(self, pod: Pod, k: int = 16) -> Explanation:
+        """Why this node, and what were the alternatives: the pod's k feasible
+        nodes with the highest TotalScore and their per-plugin scores, selected
+        on the device against the cache as it is (ks_explain).  Nothing is
+        committed.  ``candidates[0]`` is the node ``schedule_pod`` would pick
+        (percentageOfNodesToScore 100); ``top_score_nodes`` of them tie for it,
+        among which upstream's selectHost picks at random."""
+        a = Arena()
+        arr, _ = pods_array([pod], a)
+        e = _abi.KsExplanation()
+        out = (_abi.KsCandidate * max(1, k))()
+        self._ok(self.lib.ks_explain(self.ctx, arr, k, C.byref(e), out))
+        cands = []
+        for i in range(e.n_candidates):
+            sc = _abi.KsNodeScore.from_buffer_copy(out[i].score)
+            cands.append(NodePluginScores(
+                self.names.get(out[i].slot, str(out[i].slot)),
+                [PluginScore(p, int(getattr(sc, f))) for p, f in SCORE_FIELDS.items()],
+                int(sc.total_score), int(out[i].slot), sc))
+        return Explanation(int(e.num_all_nodes), int(e.feasible_nodes), int(e.top_score), int(e.top_score_nodes), cands)
 
     def node_states(self, slots: Sequence[int]) -> List[_abi.KsNodeState]:
         sl = (C.c_uint32 * max(1, len(slots)))(*slots)
