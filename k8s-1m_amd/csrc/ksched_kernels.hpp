@@ -175,7 +175,7 @@ struct SpreadArgs {
   // filter pass over the window; win_st [nslots] bit 0 in the node list, bit 1
   // feasible; win [WIN_WORDS] 0 nextStartNodeIndex, 1 the window's first slot,
   // 2 its end slot (exclusive, round the list), 3 every node visited, then
-  // [2 per 4096-slot chunk] the chunk's list / feasible counts
+  // [2 per 1024-slot chunk] the chunk's list / feasible counts
   uint32_t *win;
   uint8_t *win_st;
   uint32_t nslots;

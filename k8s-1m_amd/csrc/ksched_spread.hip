@@ -675,9 +675,12 @@ __global__ __launch_bounds__(SP_THREADS) void spread_score_kernel(SpreadArgs a) 
 // numFeasibleNodesToFind(pct, len(list)): the window is the nodes before it,
 // k feasible ones and the infeasible ones among them (fewer than k + 1
 // feasible: every node).  nextStartNodeIndex += processed, modulo the present
-// nodes.  One workgroup: per-thread counts over a contiguous slot range, a
-// block scan, then the two threads whose ranges hold the start rank and the
-// stopping rank walk them.
+// nodes, where processed counts the window and the present nodes outside the
+// PreFilterResult (a.evaluated - nl: their status is recorded too, as in
+// ks_result.evaluated_nodes), so a pod whose list is visited whole leaves the
+// index where it was.  One workgroup: per-thread counts over a contiguous
+// slot range, a block scan, then the two threads whose ranges hold the start
+// rank and the stopping rank walk them.
 constexpr int WIN_THREADS = 1024;
 // slots per count of spread_wcount_kernel (one walk step of the window);
 // ksched_host.cpp sizes win[] with the same value (WIN_CHUNK_SLOTS)
@@ -831,7 +834,8 @@ __global__ __launch_bounds__(WIN_THREADS) void spread_window_kernel(SpreadArgs a
     a.win[1] = s0;
     a.win[2] = x;
     a.win[3] = all ? 1u : 0u;
-    if (a.evaluated) a.win[0] = (uint32_t)(((uint64_t)next + processed) % a.evaluated);  // % len(allNodes)
+    // processed + the PreFilterResult exclusions, % len(allNodes)
+    if (a.evaluated) a.win[0] = (uint32_t)(((uint64_t)next + processed + (a.evaluated - nl)) % a.evaluated);
   }
 }
 

@@ -1315,13 +1315,18 @@ struct oracle {
   // it is this loop.  The node list is the present nodes in slot order
   // (upstream: the snapshot's list order), without the nodes a NodeAffinity
   // PreFilterResult excludes (upstream visits only the PreFilterResult's
-  // nodes; they keep their KS_FAIL_PREFILTER_RESULT status here, never
+  // nodes; the others keep their KS_FAIL_PREFILTER_RESULT status here, never
   // visited).  Visiting starts at nextStartNodeIndex % len(list) and goes
   // round the list; the worker cancels at the (k+1)-th feasible node, so the
-  // processed nodes (len(feasibleNodes) + len(NodeToStatus)) are the nodes
-  // before it: k feasible and the infeasible ones between them.  Fewer than
-  // k+1 feasible: every node is processed.  nextStartNodeIndex = (it +
-  // processed) % len(allNodes).  Nodes after the window get kNotVisited.
+  // visited nodes are the nodes before it: k feasible and the infeasible ones
+  // between them.  Fewer than k+1 feasible: every node of the list is
+  // visited.  The processed nodes are len(feasibleNodes) +
+  // len(NodeToStatusMap): the visited ones and the present nodes outside the
+  // PreFilterResult, whose status is recorded too (the same count as
+  // ks_result.evaluated_nodes).  nextStartNodeIndex = (it + processed) %
+  // len(allNodes); a pod whose list is visited whole, a PreFilterResult pod
+  // naming fewer than 100 nodes for one, leaves it where it was.  Nodes
+  // after the window get kNotVisited.
   void window() {
     const uint32_t N = (uint32_t)nodes.size();
     std::vector<uint32_t> list;
@@ -1340,7 +1345,7 @@ struct oracle {
         }
       for (uint64_t j = processed; j < nl; ++j) ev[list[(s + j) % nl]].status = kNotVisited;
     }
-    if (n_present) next_start = (next_start + processed) % (uint64_t)n_present;
+    if (n_present) next_start = (next_start + processed + ((uint64_t)n_present - nl)) % (uint64_t)n_present;
   }
 
   // schedulePod (schedule_one.go): findNodesThatFitPod -> prioritizeNodes -> selectHost.

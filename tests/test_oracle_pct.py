@@ -96,16 +96,39 @@ def test_deleted_nodes_shrink_the_list():
     assert o.next_start == (300 + 100) % 250
 
 
+def named_pod():
+    names = [NodeSelectorTerm(match_fields=[NodeSelectorRequirement("metadata.name", "In", [h])]) for h in ("h5", "h7")]
+    return [Pod("named", containers=[Container({"cpu": 100})], required_terms=names)]
+
+
 def test_prefilter_result_nodes_are_not_visited():
     # a pod naming two nodes (NodeAffinity PreFilterResult): the list is those
-    # two (fewer than 100: all processed); the other nodes keep their
-    # PreFilterResult status; nextStartNodeIndex moves by the two processed
-    names = [NodeSelectorTerm(match_fields=[NodeSelectorRequirement("metadata.name", "In", [h])]) for h in ("h5", "h7")]
-    p = [Pod("named", containers=[Container({"cpu": 100})], required_terms=names)]
-    r, o = run(cluster(300), p, 5)
+    # two (fewer than 100: both visited); the other 298 nodes are not visited
+    # and keep their PreFilterResult status.  processedNodes is
+    # len(feasibleNodes) + len(NodeToStatusMap), the same count as
+    # evaluated_nodes: the 2 feasible nodes and the 298 recorded statuses, so
+    # nextStartNodeIndex = (0 + 2 + 298) % 300 = 0
+    r, o = run(cluster(300), named_pod(), 5)
     assert r["node_index"][0] == 5 and r["feasible"][0] == 2 and r["evaluated"][0] == 300
     assert r["fail"][0][7] == 298  # KS_FAIL_PREFILTER_RESULT
-    assert o.next_start == 2
+    assert o.next_start == 0
+
+
+def test_prefilter_result_pod_leaves_the_next_window_in_place():
+    # 300 equal nodes, pct 5: k = 100.  A plain pod takes the window [0, 100)
+    # and leaves nextStartNodeIndex at 100.  The pod naming h5 and h7 then
+    # processes 2 + 298 nodes: (100 + 300) % 300 = 100 again.  The following
+    # plain pod's window is slots 100..199 (stopped by slot 200): it lands on
+    # slot 100, the lowest of the window's equal scores
+    a = Arena()
+    r, o = run(cluster(300), pods(1), 5, a=a)
+    assert r["node_index"][0] == 0 and o.next_start == 100
+    r, o = run(None, named_pod(), 5, o, a)
+    assert (r["node_index"][0], r["feasible"][0], r["evaluated"][0], r["fail"][0][7]) == (5, 2, 300, 298)
+    assert o.next_start == 100
+    r, o = run(None, pods(1, 1), 5, o, a)
+    assert (r["node_index"][0], r["feasible"][0], r["evaluated"][0]) == (100, 100, 100)
+    assert o.next_start == 200
 
 
 def test_pct_100_keeps_every_result():
