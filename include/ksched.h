@@ -685,6 +685,14 @@ ks_status ks_debug_counters(ks_ctx *ctx, uint64_t out[16]);
  * groups, [6] pods per group, [7] 0.  Host only; all zero before the first
  * launch of that kind. */
 ks_status ks_debug_sweep_geometry(ks_ctx *ctx, int32_t ext, uint64_t out[8]);
+/* Domain table of one topology key of the one-pod chain, so a test knows
+ * which of the chain's paths its key takes: out[0] the key's domain-id count
+ * (distinct non-empty values issued since the column was last built, plus 1
+ * for the value ""), [1] entries per constraint of the domain scratch
+ * (shared by all keys), [2] times churn has renumbered the key since ks_open,
+ * [3] domains holding two or more nodes.  Host only; all zero while no
+ * constraint or term has named the key. */
+ks_status ks_debug_topology(ks_ctx *ctx, const char *key, uint64_t out[4]);
 /* Diagnostics of the parallel commit: with the profile
  * on, every round accumulates s_memtime cycles per phase: out[0] stage,
  * [1] gather barrier, [2] proposals, [3] wave 0's row DMA issue, [4] chunk

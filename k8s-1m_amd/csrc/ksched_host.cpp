@@ -227,6 +227,7 @@ struct TopoKey {
   std::vector<uint32_t> slot_dom;   // [cap] domain of each slot (DOM_NONE: absent / no key)
   std::vector<uint32_t> dom_nodes;  // [ndom]
   uint32_t shared = 0;              // domains holding two or more nodes
+  uint64_t builds = 0;              // topo_build calls: the first creates the column, each later one renumbers it
   void place(uint32_t slot, uint32_t d) {
     const uint32_t o = slot_dom[slot];
     if (o == d) return;
@@ -2211,6 +2212,7 @@ ks_status topo_build(ks_ctx *c, uint32_t ti) {
   k.slot_dom.assign(c->cap, DOM_NONE);
   k.dom_nodes.clear();
   k.shared = 0;
+  k.builds++;
   std::vector<uint32_t> col(c->npos, DOM_NONE);
   for (uint32_t sl = 0; sl < c->cap; ++sl)
     if (c->nodes[sl].present) {
@@ -5428,6 +5430,22 @@ ks_status ks_debug_sweep_geometry(ks_ctx *c, int32_t ext, uint64_t out[8]) {
   if (!c || !out) return KS_ERR_INVALID;
   if (ks_status dst_ = drain_async(c)) return dst_;
   std::memcpy(out, c->sweep_geom[ext ? 1 : 0], sizeof c->sweep_geom[0]);
+  return KS_OK;
+}
+
+ks_status ks_debug_topology(ks_ctx *c, const char *key, uint64_t out[4]) {
+  if (!c || !key || !out) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  std::memset(out, 0, 4 * sizeof(uint64_t));
+  std::lock_guard<std::mutex> g(c->mu);
+  const int32_t id = c->lookup(key);
+  const auto it = id < 0 ? c->topo_of.end() : c->topo_of.find((uint32_t)id);
+  if (it == c->topo_of.end()) return KS_OK;
+  const TopoKey &k = c->topo[it->second];
+  out[0] = k.ndom;
+  out[1] = c->dom_cap;
+  out[2] = k.builds - 1;
+  out[3] = k.shared;
   return KS_OK;
 }
 

@@ -377,7 +377,7 @@ KSCHED_SYMBOLS = [
     "ks_batch_results", "ks_batch_free", "ks_batch_submit", "ks_batch_wait", "ks_pods_check", "ks_plugin_scores", "ks_node_states", "ks_comm_unique_id", "ks_comm_init_local", "ks_snapshot_update",
     "ks_comm_init", "ks_comm_allreduce_max", "ks_get_stats", "ks_reset_stats", "ks_set_timing",
     "ks_debug_counters", "ks_debug_set_profile", "ks_debug_resolve_profile", "ks_debug_round_record", "ks_set_sync_timeout", "ks_debug_stall", "ks_batch_marks",
-    "ks_debug_runs_started", "ks_next_start_index", "ks_debug_sweep_geometry",
+    "ks_debug_runs_started", "ks_next_start_index", "ks_debug_sweep_geometry", "ks_debug_topology",
     "ks_set_fit_strategy", "ks_get_fit_strategy", "ks_set_fit_strategy_shape", "ks_get_fit_shape", "ks_fit_shape_table",
     "ks_set_fit_strategy_resources", "ks_get_fit_resources",
     "ks_set_balanced_resources", "ks_get_balanced_resources",
@@ -474,6 +474,7 @@ def ksched_lib() -> C.CDLL:
                                        P(C.c_size_t)]
     L.ks_debug_counters.argtypes = [vp, P(C.c_uint64)]
     L.ks_debug_sweep_geometry.argtypes = [vp, C.c_int32, P(C.c_uint64)]
+    L.ks_debug_topology.argtypes = [vp, C.c_char_p, P(C.c_uint64)]
     L.ks_debug_set_profile.argtypes = [vp, C.c_int32]
     L.ks_debug_resolve_profile.argtypes = [vp, P(C.c_uint64)]
     L.ks_set_sync_timeout.argtypes = [vp, C.c_uint32]

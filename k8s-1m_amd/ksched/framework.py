@@ -560,6 +560,14 @@ class Scheduler:
         self._ok(self.lib.ks_get_stats(self.ctx, C.byref(s)))
         return s
 
+    def debug_topology(self, key: str):
+        """(domain ids, scratch entries per constraint, renumberings, domains of
+        two or more nodes) of a topology key's column (ks_debug_topology); all
+        zero while no constraint or term has named the key."""
+        out = (C.c_uint64 * 4)()
+        self._ok(self.lib.ks_debug_topology(self.ctx, key.encode(), out))
+        return tuple(int(v) for v in out)
+
     def reset_stats(self):
         self._ok(self.lib.ks_reset_stats(self.ctx))
 

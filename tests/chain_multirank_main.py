@@ -31,7 +31,7 @@ from helpers import res_array, states_np  # noqa: E402
 from ksched import Scheduler  # noqa: E402
 
 FAMILIES = {"fit": "fit_workloads", "rtcr": "rtcr_workloads", "xfit": "xfit_workloads", "ba": "ba_workloads",
-            "ports": "ports_workloads"}
+            "ports": "ports_workloads", "chain_edges": "chain_edge_cases"}
 
 
 def main(cfg):
