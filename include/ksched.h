@@ -917,6 +917,53 @@ typedef struct {
  * answers from its own replica of the node table, with no exchange. */
 ks_status ks_diagnose(ks_ctx *ctx, const ks_pod *pod, ks_diagnosis *d, ks_reason *out, uint32_t cap, uint32_t *n);
 
+/* ks_diagnose for a list of pods in one call: one compile,
+ * one upload, one pass over the node rows for every group of pods without
+ * spread constraints, InterPodAffinity records, extended resources, present
+ * images or host ports (those pods take ks_diagnose's pass, launched back to
+ * back), one read-back and one wait.  Byte-identical compiled pods (a
+ * deployment's replicas) are diagnosed once.
+ *
+ * out[i], with its rows reasons[out[i].first_reason .. + out[i].d.n_reasons),
+ * is what ks_diagnose(ctx, &pods[i], ...) returns at the moment of the call:
+ * the same fields, the same rows in the same order, equal strings,
+ * prefilter_msg included.  Every pod is answered against the one cache state
+ * the call finds, and the call shares ks_diagnose's rules: it waits for
+ * submitted batches, commits nothing, interns nothing, leaves
+ * nextStartNodeIndex alone, is over every present node whatever
+ * percentage_of_nodes_to_score, and on a multi-rank context answers from the
+ * rank's own replica of the node table.
+ *
+ * A pod ks_pods_check refuses gets that status in out[i].status, a zeroed
+ * diagnosis and no rows; the other pods are still answered, the call returns
+ * the first refused pod's status and ks_last_error names its index (the
+ * convention of ks_pods_check).  A device error ends the call.  *n_reasons is
+ * the total row count; with cap below it the call returns KS_ERR_INVALID with
+ * *n_reasons and every out[i] set and no row written (it takes precedence over
+ * a refusal's status).  n x 96 rows always suffice.  n == 0 is KS_OK; a null
+ * ctx or n_reasons, null pods or out with n > 0, or null reasons with cap > 0
+ * is KS_ERR_INVALID.
+ *
+ * The reason strings and prefilter_msg live in storage of their own, valid
+ * until the next ks_diagnose_pods or ks_close; the call leaves the strings of
+ * an earlier ks_diagnose valid, and ks_diagnose leaves this call's. */
+typedef struct {
+  ks_status status;       /* KS_OK, or the status ks_diagnose returns for this pod */
+  uint32_t first_reason;  /* this pod's rows: reasons[first_reason .. first_reason + d.n_reasons) */
+  ks_diagnosis d;         /* exactly as ks_diagnose fills it (zeroed when status != KS_OK) */
+} ks_pod_diagnosis;
+
+ks_status ks_diagnose_pods(ks_ctx *ctx, const ks_pod *pods, uint32_t n, ks_pod_diagnosis *out,
+                           ks_reason *reasons, uint32_t cap, uint32_t *n_reasons);
+/* The most recent ks_diagnose_pods call (tests prove by it which path ran):
+ * [0] distinct pods the multi-pod kernel answered, [1] distinct pods answered
+ * by the per-pod pass, [2] identical pods not diagnosed again, [3] pods run
+ * again per pod because their multi-taint entries did not fit their list,
+ * [4] launches of the multi-pod kernel, [5] its pods per group, [6] node
+ * positions one launch covers before its grid-stride loop takes a second turn
+ * ([5] and [6] are constants of the build, set before any call), [7] 0. */
+ks_status ks_debug_diagnose_pods(ks_ctx *ctx, uint64_t out[8]);
+
 /* FitError.Error() without the PostFilter part; pure host code, needs no
  * context (as ks_host_ports_conflict): "0/<num_all_nodes> nodes are
  * available:", then " <prefilter_msg>." when it is set, else the reasons with

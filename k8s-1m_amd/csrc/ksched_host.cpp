@@ -608,6 +608,18 @@ struct ks_ctx {
   uint32_t *d_diag_list = nullptr;
   std::vector<std::string> diag_strs;
   std::string diag_prefilter;
+  // ks_diagnose_pods: the multi-pod pass's shared list of
+  // (pod, slot) pairs ([DP_LIST_PER_NODE x cap]) with its counter, the per-pod
+  // passes' list shares ([DP_LIST_PER_NODE x cap] slots, split among the
+  // call's one-pod-chain pods); strings of the last call, in storage of their
+  // own (ks_diagnose's stay valid across a call and the other way round);
+  // the last call's counters (ks_debug_diagnose_pods)
+  DiagPair *d_dp_list = nullptr;
+  unsigned long long *d_dp_list_n = nullptr;
+  uint32_t *d_dp_solo_list = nullptr;
+  std::vector<std::string> dp_strs;
+  std::string dp_prefilter;
+  uint64_t dp_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // ks_explain: the blocks' key lists and tie pairs, the
   // final keys and the record, allocated by the first call
   struct ExplainDev {
@@ -5120,6 +5132,315 @@ ks_status ks_diagnose(ks_ctx *c, const ks_pod *pod, ks_diagnosis *dg, ks_reason 
 ks_status ks_fit_error_message(uint32_t num_all_nodes, const char *prefilter_msg, const ks_reason *reasons, uint32_t n,
                                char *buf, size_t cap, size_t *len) {
   return fit_error_message(num_all_nodes, prefilter_msg, reasons, n, buf, cap, len);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ks_diagnose_pods' list capacities, relative to the node capacity: pairs of
+// the multi-pod pass's shared list, and slots shared out among the per-pod
+// passes of one call
+constexpr size_t DP_LIST_PER_NODE = 4;
+
+// One pod through ks_diagnose's pass with the whole list, waited for: a pod of
+// ks_diagnose_pods whose multi-taint entries did not fit.  d is a one-pod-chain
+// descriptor (PF_SOLO, solo_off valid in w).
+ks_status diagnose_pods_rerun(ks_ctx *c, const PodDev &d, const std::vector<uint64_t> &w, DiagRec *rec,
+                              std::vector<uint32_t> *multi) {
+  ks_status s;
+  const size_t bytes = sizeof(PodDev) + w.size() * 8 + sizeof(DiagRec) + 2048;
+  if ((s = xfer_begin(c, bytes, bytes))) return s;
+  PodDev *d_pod = dscratch<PodDev>(c, 1);
+  uint64_t *d_cl = dscratch<uint64_t>(c, w.size());
+  if ((s = h2d(c, d_pod, &d, sizeof d)) || (s = h2d(c, d_cl, w.data(), w.size() * 8))) return s;
+  SpreadArgs sa = spread_args(c);
+  sa.pods = d_pod;
+  sa.clauses = d_cl;
+  sa.pod = 0;
+  sa.no_commit = 1;
+  const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(w.data() + d.solo_off);
+  sa.ports_conflict = hd->ports;
+  const DiagArgs ga{c->d_diag_rec, c->d_diag_list, c->cap};
+  HIPC(c, launch_diagnose(sa, ga, solo_needs(hd).passes, c->stream));
+  if ((s = d2h(c, rec, c->d_diag_rec, sizeof *rec)) || (s = xfer_sync(c))) return s;
+  if (rec->n_multi > c->cap) return c->fail(KS_ERR_DEVICE, "diagnose: %u listed nodes for %u slots", rec->n_multi, c->cap);
+  multi->resize(rec->n_multi);
+  if (!rec->n_multi) return KS_OK;
+  if ((s = xfer_begin(c, (size_t)rec->n_multi * 4 + 1024, 0)) ||
+      (s = d2h(c, multi->data(), c->d_diag_list, (size_t)rec->n_multi * 4)) || (s = xfer_sync(c)))
+    return s;
+  return KS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// FitError's reasons of a list of pods: the accepted pods
+// compiled as a batch compiles them, byte-identical ones diagnosed once; pods
+// without a one-pod program evaluated in groups on every node row
+// (ksched_diag_batch.hip), the others through ks_diagnose's pass back to back;
+// one read-back and one wait, then the list's used prefix.
+ks_status ks_diagnose_pods(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_pod_diagnosis *out, ks_reason *reasons,
+                           uint32_t cap, uint32_t *n_reasons) {
+  if (!c || !n_reasons || (n && (!pods || !out)) || (cap && !reasons)) return KS_ERR_INVALID;
+  *n_reasons = 0;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  uint64_t ctr[8] = {0, 0, 0, 0, 0, (uint64_t)DPB_GROUP, (uint64_t)DPB_MAX_BLOCKS * DPB_THREADS, 0};
+  std::memcpy(c->dp_ctr, ctr, sizeof ctr);
+  if (!n) return KS_OK;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  ks_status st = KS_OK, first = KS_OK;
+  std::string first_err;
+  std::vector<ks_pod> acc;       // the accepted pods
+  std::vector<uint32_t> acc_of;  // ... their indices in pods
+  std::vector<PodDev> dev;
+  ProgBuf cl;
+  uint64_t epoch0;
+  uint32_t num_all;
+  DiagNames nm;
+  {
+    std::unique_lock<std::mutex> g(c->mu);
+    for (uint32_t i = 0; i < n; ++i) {  // ks_pods_check's verdict on each pod, with its status and text
+      PodDev d0;
+      ProgBuf cl0;
+      std::memset(&out[i], 0, sizeof out[i]);
+      if ((out[i].status = compile_batch(c, &pods[i], 1, &d0, cl0, g))) {
+        if (!first) {
+          first = out[i].status;
+          std::lock_guard<std::mutex> ge(c->err_mu);
+          first_err = "pod " + std::to_string(i) + ": " + c->err;
+        }
+        continue;
+      }
+      acc.push_back(pods[i]);
+      acc_of.push_back(i);
+    }
+    epoch0 = c->class_epoch;
+    dev.resize(std::max<size_t>(acc.size(), 1));
+    if (!acc.empty()) {
+      c->compile_for_dump = true;  // no host-port triple interned
+      st = compile_batch(c, acc.data(), (uint32_t)acc.size(), dev.data(), cl, g, true);
+      c->compile_for_dump = false;
+      if (!st) st = upload_dirty_ext(c, c->xm);
+      if (!st) st = spread_alloc(c);  // the position -> slot column
+      if (!st && !c->d_diag_rec && !(st = dalloc(c, &c->d_diag_rec, 1))) st = dalloc(c, &c->d_diag_list, c->cap);
+      if (!st && !c->d_dp_list && !(st = dalloc(c, &c->d_dp_list, DP_LIST_PER_NODE * c->cap)) &&
+          !(st = dalloc(c, &c->d_dp_list_n, 1)))
+        st = dalloc(c, &c->d_dp_solo_list, DP_LIST_PER_NODE * c->cap);
+    }
+    num_all = c->n_present;
+    for (size_t b = 0; b < c->hard_list.size() && b < (size_t)DIAG_TAINT_BINS; ++b)
+      nm.taint[b] = diag_taint_reason(c->strs[c->hard_list[b].key], c->strs[c->hard_list[b].value]);
+    for (size_t x = 0; x < c->xres_names.size() && x < 8; ++x) nm.xres[x] = c->strs[c->xres_names[x]];
+  }
+  // selector classes the compile created are dropped again below, whatever happens in between
+  auto drop_classes = [&] {
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int k = 0; k < MAX_CLASSES; ++k) {
+      SpreadClass &sc = c->classes[k];
+      if (!sc.live || sc.born <= epoch0 || sc.refs) continue;
+      c->class_of.erase(sc.canon);
+      sc = SpreadClass();
+    }
+  };
+  const uint32_t m = (uint32_t)acc.size();
+  // identical compiled pods (descriptor and program words) are diagnosed once: rep[j] the first of j's class
+  std::vector<uint32_t> rep(m), order;  // order: the distinct pods -- plain without PF_EXT, plain with, one-pod chain
+  uint32_t n_plain = 0, n_ext = 0, n_solo = 0;
+  if (!st && m) {
+    std::unordered_map<uint64_t, uint32_t> seen;
+    seen.reserve(m);
+    for (uint32_t j = 0; j < m; ++j) {
+      PodDev x = dev[j];
+      x.req_off = x.pref_off = x.solo_off = x.pre_off = 0;
+      uint64_t h = 1469598103934665603ull;  // FNV-1a over the descriptor's words (pod_classes)
+      const uint64_t *w = reinterpret_cast<const uint64_t *>(&x);
+      for (size_t q = 0; q < sizeof(PodDev) / 8; ++q) h = (h ^ w[q]) * 1099511628211ull;
+      rep[j] = j;
+      for (;; ++h) {
+        auto it = seen.find(h);
+        if (it == seen.end()) {
+          seen.emplace(h, j);
+          break;
+        }
+        if (same_pod_program(dev[it->second], dev[j], cl.w.data())) {
+          rep[j] = it->second;
+          break;
+        }
+      }
+    }
+    for (int kind = 0; kind < 3; ++kind)
+      for (uint32_t j = 0; j < m; ++j) {
+        if (rep[j] != j) continue;
+        const int k = (dev[j].flags & PF_SOLO) ? 2 : (dev[j].flags & PF_EXT) ? 1 : 0;
+        if (k != kind) continue;
+        order.push_back(j);
+        ++(k == 0 ? n_plain : k == 1 ? n_ext : n_solo);
+      }
+  }
+  const uint32_t D = (uint32_t)order.size();
+  std::vector<uint32_t> at(m, 0);  // distinct pod -> its index in order
+  for (uint32_t k = 0; k < D; ++k) at[order[k]] = k;
+  // an empty one-pod program, for a plain pod that has to take ks_diagnose's pass after all
+  if (cl.w.size() & 1) cl.w.push_back(0);
+  const uint32_t empty_solo = (uint32_t)cl.w.size();
+  cl.w.resize(cl.w.size() + sizeof(SoloHdr) / 8, 0);
+  struct Tail {
+    unsigned long long list_n;
+    uint64_t _pad;
+  };
+  std::vector<DiagRec> recs(D);
+  std::vector<std::vector<uint32_t>> listed(D);  // slots of the nodes with several untolerated taints, per pod
+  const size_t list_cap = DP_LIST_PER_NODE * c->cap;
+  const uint32_t share = n_solo ? (uint32_t)std::min<size_t>(c->cap, list_cap / n_solo) : 0;
+  std::vector<uint32_t> again;  // pods whose listed entries did not all fit
+  if (!st && D) st = [&]() -> ks_status {
+    ks_status s;
+    std::vector<PodDev> hp(D);
+    for (uint32_t k = 0; k < D; ++k) hp[k] = dev[order[k]];
+    const size_t back = (size_t)D * sizeof(DiagRec);
+    const size_t bytes = (size_t)D * sizeof(PodDev) + cl.w.size() * 8 + back + 4096;
+    if ((s = xfer_begin(c, bytes, bytes))) return s;
+    PodDev *d_pods = dscratch<PodDev>(c, D);
+    uint64_t *d_cl = dscratch<uint64_t>(c, cl.w.size());
+    DiagRec *d_recs = dscratch<DiagRec>(c, D);
+    if (!d_pods || !d_cl || !d_recs) return c->fail(KS_ERR_INVALID, "diagnose_pods: device scratch overflow");
+    if ((s = h2d(c, d_pods, hp.data(), (size_t)D * sizeof(PodDev))) || (s = h2d(c, d_cl, cl.w.data(), cl.w.size() * 8)))
+      return s;
+    HIPC(c, hipMemsetAsync(d_recs, 0, back, c->stream));
+    HIPC(c, hipMemsetAsync(c->d_dp_list_n, 0, sizeof(unsigned long long), c->stream));
+    SpreadArgs sa = spread_args(c);
+    DiagPodsArgs pa{};
+    pa.t = sa.t;
+    pa.pos_slot = sa.pos_slot;
+    pa.npos = sa.npos;
+    pa.pods = d_pods;
+    pa.clauses = d_cl;
+    pa.recs = d_recs;
+    pa.list = c->d_dp_list;
+    pa.list_n = c->d_dp_list_n;
+    pa.list_cap = (uint32_t)std::min<size_t>(list_cap, 0xFFFFFFFFu);
+    pa.first = 0;
+    pa.count = n_plain;
+    HIPC(c, launch_diagnose_pods(pa, false, c->stream));
+    pa.first = n_plain;
+    pa.count = n_ext;
+    HIPC(c, launch_diagnose_pods(pa, true, c->stream));
+    c->dp_ctr[4] = (n_plain ? 1 : 0) + (n_ext ? 1 : 0);
+    // the one-pod-chain pods: ks_diagnose's chain for each, back to back, into its own record and list share
+    sa.pods = d_pods;
+    sa.clauses = d_cl;
+    sa.no_commit = 1;
+    for (uint32_t k = n_plain + n_ext; k < D; ++k) {
+      const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + hp[k].solo_off);
+      sa.pod = k;
+      sa.ports_conflict = hd->ports;  // (the program holds the conflict mask itself: PORTS_DUMP)
+      const DiagArgs ga{d_recs + k, c->d_dp_solo_list + (size_t)(k - n_plain - n_ext) * share, share};
+      HIPC(c, launch_diagnose(sa, ga, solo_needs(hd).passes, c->stream));
+    }
+    Tail tail{};
+    if ((s = d2h(c, recs.data(), d_recs, back)) || (s = d2h(c, &tail, c->d_dp_list_n, sizeof tail.list_n)) ||
+        (s = xfer_sync(c)))
+      return s;
+    // the lists' used prefixes, in one more wait
+    const size_t used = (size_t)std::min<unsigned long long>(tail.list_n, pa.list_cap);
+    std::vector<DiagPair> pairs(used);
+    size_t pin = used * sizeof(DiagPair) + 1024;
+    for (uint32_t k = n_plain + n_ext; k < D; ++k) pin += xround((size_t)std::min(recs[k].n_multi, share) * 4);
+    if (pin > 1024) {
+      if ((s = xfer_begin(c, pin, 0)) || (s = d2h(c, pairs.data(), c->d_dp_list, used * sizeof(DiagPair)))) return s;
+      for (uint32_t k = n_plain + n_ext; k < D; ++k) {
+        if (recs[k].n_multi > c->cap)
+          return c->fail(KS_ERR_DEVICE, "diagnose_pods: %u listed nodes for %u slots", recs[k].n_multi, c->cap);
+        if (recs[k].n_multi > share) continue;  // run again below
+        listed[k].resize(recs[k].n_multi);
+        if ((s = d2h(c, listed[k].data(), c->d_dp_solo_list + (size_t)(k - n_plain - n_ext) * share,
+                     (size_t)recs[k].n_multi * 4)))
+          return s;
+      }
+      if ((s = xfer_sync(c))) return s;
+    }
+    for (const DiagPair &p : pairs) {
+      if (p.pod >= n_plain + n_ext) return c->fail(KS_ERR_DEVICE, "diagnose_pods: listed pod %u of %u", p.pod, D);
+      listed[p.pod].push_back(p.slot);
+    }
+    for (uint32_t k = 0; k < D; ++k)
+      if (listed[k].size() != recs[k].n_multi) again.push_back(k);
+    // ... and the pods that lost entries, one at a time with the whole list
+    for (uint32_t k : again) {
+      PodDev d = hp[k];
+      if (!(d.flags & PF_SOLO)) {
+        d.flags |= PF_SOLO;
+        d.solo_off = empty_solo;
+      }
+      if ((s = diagnose_pods_rerun(c, d, cl.w, &recs[k], &listed[k]))) return s;
+    }
+    return KS_OK;
+  }();
+  if (m) drop_classes();
+  if (st) return st;
+  c->dp_ctr[0] = n_plain + n_ext;
+  c->dp_ctr[1] = n_solo;
+  c->dp_ctr[2] = m - D;
+  c->dp_ctr[3] = again.size();
+  // rows per distinct pod, then every pod's copy
+  std::vector<std::vector<DiagRow>> rows(D);
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    for (uint32_t k = 0; k < D; ++k) {
+      const PodDev &d = dev[order[k]];
+      // a node with several untolerated taints reports the first in its own taint order
+      for (uint32_t slot : listed[k]) {
+        if (slot >= c->cap) return c->fail(KS_ERR_DEVICE, "diagnose_pods: listed slot %u >= capacity", slot);
+        for (auto &t : c->nodes[slot].hard_taints) {
+          auto it = c->hard_dict.find(TaintKey{t[0], t[1], (int32_t)t[2]});
+          if (it == c->hard_dict.end() || (d.tol_hard >> it->second & 1ull)) continue;
+          recs[k].taint[it->second]++;
+          break;
+        }
+      }
+      diag_rows(recs[k], nm, d.flags & PF_NA_CONFLICT, &rows[k]);
+    }
+  }
+  c->dp_strs.clear();
+  c->dp_prefilter = REASON_AFFINITY_CONFLICT;
+  std::vector<size_t> str0(D);  // first string of each distinct pod's rows
+  for (uint32_t k = 0; k < D; ++k) {
+    str0[k] = c->dp_strs.size();
+    for (DiagRow &r : rows[k]) c->dp_strs.push_back(std::move(r.reason));
+  }
+  uint64_t total = 0;
+  for (uint32_t j = 0; j < m; ++j) total += rows[at[rep[j]]].size();
+  if (total > 0xFFFFFFFFull) return c->fail(KS_ERR_INVALID, "diagnose_pods: %llu reasons", (unsigned long long)total);
+  *n_reasons = (uint32_t)total;
+  uint32_t next = 0;
+  for (uint32_t j = 0; j < m; ++j) {
+    const uint32_t k = at[rep[j]];
+    ks_pod_diagnosis &o = out[acc_of[j]];
+    const bool conflict = dev[order[k]].flags & PF_NA_CONFLICT;
+    diag_counts(recs[k], &o.d);
+    o.d.num_all_nodes = num_all;
+    o.d.n_reasons = (uint32_t)rows[k].size();
+    o.d.prefilter_msg = conflict ? c->dp_prefilter.c_str() : nullptr;
+    o.first_reason = next;
+    if (cap >= total)
+      for (size_t i = 0; i < rows[k].size(); ++i)
+        reasons[next + i] = ks_reason{rows[k][i].plugin, rows[k][i].count, c->dp_strs[str0[k] + i].c_str()};
+    next += (uint32_t)rows[k].size();
+  }
+  if (cap < total) return c->fail(KS_ERR_INVALID, "diagnose_pods: %u reasons, room for %u", (uint32_t)total, cap);
+  if (first) return c->fail(first, "%s", first_err.c_str());
+  return KS_OK;
+}
+
+ks_status ks_debug_diagnose_pods(ks_ctx *c, uint64_t out[8]) {
+  if (!c || !out) return KS_ERR_INVALID;
+  std::memcpy(out, c->dp_ctr, sizeof c->dp_ctr);
+  out[5] = DPB_GROUP;
+  out[6] = (uint64_t)DPB_MAX_BLOCKS * DPB_THREADS;
+  return KS_OK;
 }
 
 // A pod's best nodes with their per-plugin scores: the pod

@@ -254,6 +254,34 @@ struct DiagArgs {
   uint32_t list_cap;
 };
 hipError_t launch_diagnose(const SpreadArgs &a, const DiagArgs &g, uint32_t passes, hipStream_t st);
+// ks_diagnose_pods (ksched_diag_batch.hip): the pods
+// [first, first + count) of the call, none with a one-pod program, evaluated
+// in groups of DPB_GROUP on every node row: recs[i] is pod i's record (zeroed
+// by the caller); list [list_cap]: (pod, slot) of every node with several
+// untolerated taints for a pod, *list_n (zeroed by the caller) the pairs
+// produced, which may exceed list_cap; recs[i].n_multi counts pod i's.
+constexpr int DPB_THREADS = 512;      // lanes of a block, one node position each per grid-stride turn
+constexpr int DPB_GROUP = 64;         // pods per group (grid.y): LDS 64 x 89 counters = 22,784 B
+constexpr int DPB_STAGE = 2048;       // (pod, slot) pairs a block stages per turn before it reserves list room: 16 KB
+constexpr int DPB_MAX_BLOCKS = 512;   // grid.x: more positions take further turns of the grid-stride loop
+struct DiagPair {
+  uint32_t pod, slot;
+};
+struct DiagPodsArgs {
+  NodeTable t;
+  const uint32_t *pos_slot;   // position -> slot (SLOT_NONE: padding)
+  uint32_t npos;
+  uint32_t first, count;
+  const PodDev *pods;
+  const uint64_t *clauses;
+  DiagRec *recs;
+  DiagPair *list;
+  unsigned long long *list_n;
+  uint32_t list_cap;
+};
+// ext: the pods read taint / label / name columns (all of them have PF_EXT, or none)
+hipError_t launch_diagnose_pods(const DiagPodsArgs &a, bool ext, hipStream_t st);
+uint32_t diagnose_pods_blocks(uint32_t npos);  // grid.x of a launch over npos positions
 // the chain's front for a.pod without a window: [prep + min], the filter pass
 // launch_spread_pod would choose for `passes`, [score]; the accumulators and
 // the per-position columns (st, part, raw, ipa_raw) stay as the select pass

@@ -343,6 +343,10 @@ class KsDiagnosis(C.Structure):  # ks_diagnosis (ks_diagnose)
                 ("node_ports_nodes", C.c_uint32), ("n_reasons", C.c_uint32), ("prefilter_msg", C.c_char_p)]
 
 
+class KsPodDiagnosis(C.Structure):  # ks_pod_diagnosis (ks_diagnose_pods)
+    _fields_ = [("status", C.c_int32), ("first_reason", C.c_uint32), ("d", KsDiagnosis)]
+
+
 class KsCandidate(C.Structure):  # ks_candidate (ks_explain)
     _fields_ = [("slot", C.c_uint32), ("_pad", C.c_uint32), ("score", KsNodeScore)]
 
@@ -383,6 +387,7 @@ KSCHED_SYMBOLS = [
     "ks_set_balanced_resources", "ks_get_balanced_resources",
     "ks_host_ports_conflict", "ks_node_used_ports",
     "ks_diagnose", "ks_fit_error_message",
+    "ks_diagnose_pods", "ks_debug_diagnose_pods",
     "ks_explain",
 ]
 KSGATHER_SYMBOLS = [
@@ -469,6 +474,8 @@ def ksched_lib() -> C.CDLL:
     L.ks_host_ports_conflict.argtypes = [P(KsHostPort), P(KsHostPort)]
     L.ks_node_used_ports.argtypes = [vp, C.c_uint32, P(KsHostPort), C.c_uint32, P(C.c_uint32)]
     L.ks_diagnose.argtypes = [vp, P(KsPod), P(KsDiagnosis), P(KsReason), C.c_uint32, P(C.c_uint32)]
+    L.ks_diagnose_pods.argtypes = [vp, P(KsPod), C.c_uint32, P(KsPodDiagnosis), P(KsReason), C.c_uint32, P(C.c_uint32)]
+    L.ks_debug_diagnose_pods.argtypes = [vp, P(C.c_uint64)]
     L.ks_explain.argtypes = [vp, P(KsPod), C.c_uint32, P(KsExplanation), P(KsCandidate)]
     L.ks_fit_error_message.argtypes = [C.c_uint32, C.c_char_p, P(KsReason), C.c_uint32, C.c_char_p, C.c_size_t,
                                        P(C.c_size_t)]

@@ -493,6 +493,43 @@ class Scheduler:
         return FitDiagnosis(int(d.num_all_nodes), int(d.feasible_nodes), [int(v) for v in d.plugin_nodes],
                             int(d.node_ports_nodes), reasons, pm, fit_error_message(int(d.num_all_nodes), rows, pm))
 
+    def diagnose_many(self, pods: Sequence[Pod], strict: bool = True) -> List[Optional[FitDiagnosis]]:
+        """``diagnose`` for a list of pods in one call (ks_diagnose_pods): one
+        compile, one upload and one wait; every entry is what ``diagnose``
+        returns for that pod against the cache as the call finds it.  A pod the
+        library refuses raises KschedError when ``strict``; otherwise its entry
+        is None and the rest are still answered."""
+        a = Arena()
+        arr, n = pods_array(list(pods), a)
+        out = (_abi.KsPodDiagnosis * max(1, n))()
+        cap = max(1, n) * _abi.DIAG_MAX_REASONS
+        rows = (_abi.KsReason * cap)()
+        total = C.c_uint32()
+        st = self.lib.ks_diagnose_pods(self.ctx, arr, n, out, rows, cap, C.byref(total))
+        if st != 0 and (strict or not any(out[i].status == st for i in range(n))):
+            self._ok(st)
+        res: List[Optional[FitDiagnosis]] = []
+        for i in range(n):
+            if out[i].status != 0:
+                res.append(None)
+                continue
+            d, lo = out[i].d, out[i].first_reason
+            mine = [(rows[lo + k].reason.decode(), int(rows[lo + k].count)) for k in range(d.n_reasons)]
+            reasons: Dict[str, int] = {}
+            for r, c in mine:
+                reasons[r] = reasons.get(r, 0) + c
+            pm = d.prefilter_msg.decode() if d.prefilter_msg else None
+            res.append(FitDiagnosis(int(d.num_all_nodes), int(d.feasible_nodes), [int(v) for v in d.plugin_nodes],
+                                    int(d.node_ports_nodes), reasons, pm,
+                                    fit_error_message(int(d.num_all_nodes), mine, pm)))
+        return res
+
+    def diagnose_pods_counters(self) -> List[int]:
+        """ks_debug_diagnose_pods: which paths the last ``diagnose_many`` took."""
+        out = (C.c_uint64 * 8)()
+        self._ok(self.lib.ks_debug_diagnose_pods(self.ctx, out))
+        return [int(v) for v in out]
+
     def explain(self, pod: Pod, k: int = 16) -> Explanation:
         """Why this node, and what were the alternatives: the pod's k feasible
         nodes with the highest TotalScore and their per-plugin scores, selected
