@@ -670,7 +670,11 @@ ks_status ks_reset_stats(ks_ctx *ctx);
 /* Raw counters: [0] rounds [1] pods resolved [2] pods swept
  * [3] speculated rounds wasted [4] pods re-swept because their guessed
  * normalising maxima were wrong, [5] label-dictionary reclaims, [6] taint
- * dictionary rebuilds, [7] identical pods not swept, [12] passes of the
+ * dictionary rebuilds, [7] identical pods not swept, [9] entries of the
+ * resource-only rounds' sweep lists (sorted by cpu request) whose (cpu request,
+ * non-zero cpu request) equals their predecessor's in the same pod group, so
+ * the sweep kept its per-node cpu terms for them (tests; nothing else reads
+ * it), [12] passes of the
  * parallel commit, [13] rounds it resolved, [14] of those it cut short and
  * handed over to the serial kernel (AUTO), [15] of those resolved in one step
  * (one class of identical request-less pods).  (The instrumented stamps builds,

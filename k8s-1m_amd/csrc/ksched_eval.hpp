@@ -381,6 +381,24 @@ __device__ __forceinline__ int32_t score_ba_sum(double sc, double sm, const Node
   return (int32_t)(om * 100.0);  // in [0, 100]
 }
 
+// score_ba_sum and score_la split by resource, for the sweep that keeps a
+// node's cpu terms across the pods of one cpu request: the
+// same operations on the same operands in the same order, so every
+// intermediate is the one the unsplit functions compute.
+// One resource's fraction min(1, requested / allocatable).
+__device__ __forceinline__ double ba_fraction(double s, double alloc, double inv) {
+  return fmin(div_rn(s, alloc, inv), 1.0);
+}
+// BalancedAllocation from the two fractions (f0 cpu, f1 memory)
+__device__ __forceinline__ int32_t score_ba_fractions(double f0, double f1, const NodeRegs &r) {
+  const double om = __builtin_fma(-fabs(f0 - f1), r.bamul, 1.0);
+  return (int32_t)(om * 100.0);
+}
+// LeastAllocated from the cpu term and the pod's memory term
+__device__ __forceinline__ int32_t score_la_cpu(int32_t la_cpu, double nz100_mem, const NodeRegs &r) {
+  return (la_cpu + least_requested(r.lf100_mem, nz100_mem, r.inv_mem)) >> r.lashift;
+}
+
 __device__ __forceinline__ int32_t score_ba(const PodDev &p, const NodeRegs &r) {
   return score_ba_sum(r.rcpu + p.req_cpu_d, r.rmem + p.req_mem_d, r);
 }

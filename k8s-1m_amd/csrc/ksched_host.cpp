@@ -3182,10 +3182,16 @@ ks_status enqueue_round(ks_ctx *c, ks_batch *b, uint32_t k, uint32_t end) {
   a.marks = b->d_marks;
   const uint32_t q = k & 1u, pq = q ^ 1u;
   c->dedup_used[q] = b->dups && c->dedup;
+  uint32_t *dd = c->d_dedup + (size_t)q * (2 * MAX_P + 4);
   if (c->dedup_used[q]) {
-    uint32_t *dd = c->d_dedup + (size_t)q * (2 * MAX_P + 4);
     a.cls = b->d_cls;
     a.rep = dd;
+  }
+  // a resource-only round's sweep walks a list in cpu-key order, with or
+  // without identical pods (RoundArgs::sort_cpu); a label / taint round has a
+  // list only for its identical pods, in window order
+  a.sort_cpu = b->ext ? 0u : 1u;
+  if (c->dedup_used[q] || a.sort_cpu) {
     a.ulist = dd + MAX_P;
     a.nuniq = dd + 2 * MAX_P;
   }

@@ -64,6 +64,13 @@ __device__ __forceinline__ PodDev load_pod(const PodDev *pods, uint32_t i) {
 }
 
 
+// The value stays in one VGPR (pair) from here on: an empty asm the compiler
+// cannot look through, so it does not keep two copies alive across a loop.
+template <typename T>
+__device__ __forceinline__ void pin_vgpr(T &x) {
+  asm volatile("" : "+v"(x));
+}
+
 // ------------------------------------------------ sweep: EXT pods, NPL nodes
 // The sweep evaluates a pod's label programs term-outer, node-inner: each
 // term's words are read once per pod (scalar loads) and applied to the
@@ -252,6 +259,19 @@ void sweep_kernel(RoundArgs a) {
   }
 
   uint32_t feas_v = 0;  // resource-only: lane q holds the feasible nodes of the batch's pod q
+  // Resource-only rounds of the default strategy walk their pods in cpu-key
+  // order (cpu_sort_rank), so consecutive pods mostly share (req_cpu, nz_cpu):
+  // each node's terms that depend on the pod through cpu alone -- the
+  // BalancedAllocation fraction, the LeastAllocated term and the lane mask of
+  // pod count and cpu fit -- are kept across pods and batches and recomputed
+  // only where the key changes (wave-uniform: the pod sits in SGPRs).
+  // Requests are >= 0, so -1 matches no pod: a block's first pod recomputes.
+  constexpr bool SHARE = !EXT && GF == 0;
+  int64_t ck_req = -1, ck_nz = -1;
+  double c_f0[SHARE ? NPL : 1];
+  int32_t c_la[SHARE ? NPL : 1];
+  uint64_t c_fm[SHARE ? NPL : 1];  // SGPR pairs
+  static_for<(SHARE ? NPL : 1)>([&](auto J) { c_f0[J] = 0.0; c_la[J] = 0; c_fm[J] = 0; });
   // One pod (q: its place in the batch, resource-only kernels)
   auto sweep_pod = [&](const uint32_t it, const uint32_t q) __attribute__((always_inline)) {
     // FIX mode: slice entry it - start of the compacted flagged-pod list
@@ -281,22 +301,54 @@ void sweep_kernel(RoundArgs a) {
       // registers; a zero request's check is masked off (all-ones lane mask)
       // (lane masks of the wave-uniform conditions: SGPR pairs)
       const uint64_t zc = __builtin_amdgcn_ballot_w64(p.req_cpu == 0), zm = __builtin_amdgcn_ballot_w64(p.req_mem == 0);
-      static_for<NPL>([&](auto J) {
-        constexpr int j = J;
-        const double sc = nr[j].rcpu + p.req_cpu_d, sm = nr[j].rmem + p.req_mem_d;
-        // the wave's feasibility mask, ANDed from the compares' lane masks
-        // (SALU), selects the key and is counted by s_bcnt1: a bool here
-        // made the compiler copy the mask through a VGPR per node
-        const uint64_t fm = podfit_m[j] & (zc | __builtin_amdgcn_ballot_w64(!(sc > nr[j].acpu_d))) &
-                            (zm | __builtin_amdgcn_ballot_w64(!(sm > nr[j].amem_d)));
-        // key = (w_fit LA + w_ba BA) << 9 + kc[j]: two 24-bit multiply-adds
-        // with the weights pre-shifted (10000 << 9 < 2^24; the key < 2^31)
-        const uint32_t key = sel_mask(fm, wmad_s(wf9, (uint32_t)score_fit<GF>(p, nr[j], a.fs),
-                                                 wmad_s(wb9, (uint32_t)score_ba_sum(sc, sm, nr[j]), kc[j])));
-        b2 = max(b2, min(b1, key));
-        b1 = max(b1, key);
-        feas += (uint32_t)__popcll(fm);
-      });
+      if constexpr (SHARE) {
+        // the key is the pair: a container without a cpu request makes
+        // nz_cpu differ between pods of one req_cpu
+        if (p.req_cpu != ck_req || p.nz_cpu != ck_nz) {
+          ck_req = p.req_cpu;
+          ck_nz = p.nz_cpu;
+          static_for<NPL>([&](auto J) {
+            constexpr int j = J;
+            const double sc = nr[j].rcpu + p.req_cpu_d;
+            c_fm[j] = podfit_m[j] & (zc | __builtin_amdgcn_ballot_w64(!(sc > nr[j].acpu_d)));
+            c_la[j] = least_requested(nr[j].lf100_cpu, p.nz100_cpu, nr[j].inv_cpu);
+            c_f0[j] = ba_fraction(sc, nr[j].acpu_d, nr[j].inv_cpu);
+          });
+        }
+        // one register per kept value on both paths: without this the
+        // compiler rotates the pod loop and copies all of them on every pod
+        static_for<NPL>([&](auto J) { pin_vgpr(c_f0[J]); pin_vgpr(c_la[J]); });
+        // the memory side and the joint part, as score_la / score_ba_sum and
+        // the key build below compute them
+        static_for<NPL>([&](auto J) {
+          constexpr int j = J;
+          const double sm = nr[j].rmem + p.req_mem_d;
+          const uint64_t fm = c_fm[j] & (zm | __builtin_amdgcn_ballot_w64(!(sm > nr[j].amem_d)));
+          const double f1 = ba_fraction(sm, nr[j].amem_d, nr[j].inv_mem);
+          const uint32_t key = sel_mask(fm, wmad_s(wf9, (uint32_t)score_la_cpu(c_la[j], p.nz100_mem, nr[j]),
+                                                   wmad_s(wb9, (uint32_t)score_ba_fractions(c_f0[j], f1, nr[j]), kc[j])));
+          b2 = max(b2, min(b1, key));
+          b1 = max(b1, key);
+          feas += (uint32_t)__popcll(fm);
+        });
+      } else {
+        static_for<NPL>([&](auto J) {
+          constexpr int j = J;
+          const double sc = nr[j].rcpu + p.req_cpu_d, sm = nr[j].rmem + p.req_mem_d;
+          // the wave's feasibility mask, ANDed from the compares' lane masks
+          // (SALU), selects the key and is counted by s_bcnt1: a bool here
+          // made the compiler copy the mask through a VGPR per node
+          const uint64_t fm = podfit_m[j] & (zc | __builtin_amdgcn_ballot_w64(!(sc > nr[j].acpu_d))) &
+                              (zm | __builtin_amdgcn_ballot_w64(!(sm > nr[j].amem_d)));
+          // key = (w_fit LA + w_ba BA) << 9 + kc[j]: two 24-bit multiply-adds
+          // with the weights pre-shifted (10000 << 9 < 2^24; the key < 2^31)
+          const uint32_t key = sel_mask(fm, wmad_s(wf9, (uint32_t)score_fit<GF>(p, nr[j], a.fs),
+                                                   wmad_s(wb9, (uint32_t)score_ba_sum(sc, sm, nr[j]), kc[j])));
+          b2 = max(b2, min(b1, key));
+          b1 = max(b1, key);
+          feas += (uint32_t)__popcll(fm);
+        });
+      }
       f4 = vcount - feas;
     } else {
       // label programs once per pod for the lane's NPL nodes
@@ -1036,34 +1088,97 @@ __device__ __forceinline__ void advance_kernel_body(const RoundArgs &a) {
 // of ADV_THREADS >= P threads after the advance: thread r inserts its class
 // into an LDS hash with the lowest r as value, reads back its representative,
 // and the representatives are compacted in window order (ballot prefix sums).
+// A round without identical pods (a.rep null) lists every pod of the window;
+// a resource-only round's list is then put in cpu-key order (cpu_sort_rank).
 constexpr int ADV_THREADS = MAX_P;
 constexpr uint32_t DHASH = 2 * MAX_P;
 constexpr uint32_t NONE32 = 0xFFFFFFFFu;
+// RoundArgs::sort_cpu: the list position of representative t (u) becomes its
+// rank among the representatives by cpu key (rq, nz) = (req_cpu, nz_cpu), ties
+// by window index, so the list is one deterministic order.  P <= 256: every
+// thread counts the keys below its own over LDS (all lanes read one address,
+// a broadcast; no branch in the loop, so the reads run ahead of the
+// compares).  While every key half is below 2^28 (268,000 cores) the triple
+// (rq, nz, t) is one 64-bit word and a step one compare; otherwise the halves
+// are compared (nz < 2^46 leaves t its 8 bits).  The other threads hold a key
+// above every pod's (requests are >= 0), so they rank behind the
+// representatives and count for nobody.  Returns the representatives whose
+// key equals their list predecessor's in the same pod group of a.pg entries:
+// the evaluations whose cpu terms the sweep keeps (counters[CTR_CPU_SHARED]).
+constexpr int CPU_KEY_NARROW = 28;
+__device__ uint32_t cpu_sort_rank(const RoundArgs &a, uint32_t t, bool u, uint64_t rq, uint64_t nz, uint32_t &idx) {
+  __shared__ uint64_t s_ck[ADV_THREADS][2];  // by window index, then by rank
+  __shared__ uint32_t s_shared;
+  if (t == 0) s_shared = 0;
+  const bool wide = __syncthreads_or(u && ((rq | nz) >> CPU_KEY_NARROW) != 0);
+  uint32_t rank = 0;
+  if (!wide) {
+    uint64_t *s_k = &s_ck[0][0];
+    const uint64_t k = u ? rq << (CPU_KEY_NARROW + 8) | nz << 8 | t : ~0ull;
+    s_k[t] = k;
+    __syncthreads();
+#pragma unroll 16
+    for (uint32_t i = 0; i < (uint32_t)ADV_THREADS; ++i) rank += (uint32_t)(s_k[i] < k);
+  } else {
+    const uint64_t hi = u ? rq : ~0ull, lo = u ? nz << 8 | t : ~0ull;
+    s_ck[t][0] = hi;
+    s_ck[t][1] = lo;
+    __syncthreads();
+#pragma unroll 8
+    for (uint32_t i = 0; i < (uint32_t)ADV_THREADS; ++i) {
+      const uint64_t h2 = s_ck[i][0], l2 = s_ck[i][1];
+      rank += (uint32_t)(h2 < hi) | ((uint32_t)(h2 == hi) & (uint32_t)(l2 < lo));
+    }
+  }
+  __syncthreads();  // every key has been read by window index
+  if (u) {
+    s_ck[rank][0] = rq;
+    s_ck[rank][1] = nz;
+    idx = rank;
+  }
+  __syncthreads();
+  const uint32_t prev = u && rank % a.pg != 0 ? rank - 1 : 0;  // (entry 0 starts a group)
+  const bool same = u && rank % a.pg != 0 && ((s_ck[prev][0] ^ rq) | (s_ck[prev][1] ^ nz)) == 0;
+  const uint64_t sb = __ballot(same);
+  if (t % WAVE == 0 && sb) atomicAdd(&s_shared, (uint32_t)__popcll(sb));
+  __syncthreads();
+  return s_shared;
+}
+
 __device__ void dedup_round(const RoundArgs &a, uint32_t s) {
   __shared__ uint32_t s_k[DHASH], s_v[DHASH], s_wn[ADV_THREADS / WAVE];
   const uint32_t t = threadIdx.x, lane = t % WAVE, wid = t / WAVE;
+  const bool valid = t < a.P && s < a.npods && t < a.npods - s;
+  // the cpu key, loaded ahead of the hash (cpu_sort_rank)
+  uint64_t rq = 0, nz = 0;
+  if (a.sort_cpu && valid) {
+    rq = (uint64_t)a.pods[s + t].req_cpu;
+    nz = (uint64_t)a.pods[s + t].nz_cpu;
+  }
   for (uint32_t i = t; i < DHASH; i += ADV_THREADS) {
     s_k[i] = NONE32;
     s_v[i] = NONE32;
   }
   __syncthreads();
-  const bool valid = t < a.P && s < a.npods && t < a.npods - s;
-  const uint32_t key = valid ? a.cls[s + t] : NONE32;
-  uint32_t h = (key * 2654435761u) >> 23;  // 9 bits
-  if (valid) {
-    for (;;) {
-      const uint32_t prev = atomicCAS(&s_k[h], NONE32, key);
-      if (prev == NONE32 || prev == key) break;
-      h = (h + 1) & (DHASH - 1);
+  uint32_t rep = t;
+  if (a.rep != nullptr) {  // (kernel argument: the whole block takes one side)
+    const uint32_t key = valid ? a.cls[s + t] : NONE32;
+    uint32_t h = (key * 2654435761u) >> 23;  // 9 bits
+    if (valid) {
+      for (;;) {
+        const uint32_t prev = atomicCAS(&s_k[h], NONE32, key);
+        if (prev == NONE32 || prev == key) break;
+        h = (h + 1) & (DHASH - 1);
+      }
+      atomicMin(&s_v[h], t);
     }
-    atomicMin(&s_v[h], t);
+    __syncthreads();
+    rep = valid ? s_v[h] : t;
+    if (t < (uint32_t)MAX_P) a.rep[t] = rep;
   }
-  __syncthreads();
-  const uint32_t rep = valid ? s_v[h] : t;
   const bool u = valid && rep == t;
   const uint64_t ub = __ballot(u);
   if (lane == 0) s_wn[wid] = (uint32_t)__popcll(ub);
-  if (t < (uint32_t)MAX_P) a.rep[t] = rep;
   __syncthreads();
   uint32_t idx = (uint32_t)__popcll(ub & ((1ull << lane) - 1ull)), total = 0;
 #pragma unroll
@@ -1071,6 +1186,8 @@ __device__ void dedup_round(const RoundArgs &a, uint32_t s) {
     idx += (uint32_t)w < wid ? s_wn[w] : 0u;
     total += s_wn[w];
   }
+  uint32_t shared = 0;
+  if (a.sort_cpu) shared = cpu_sort_rank(a, t, u, rq, nz, idx);
   if (u) a.ulist[idx] = t;
   if (t == 0) {
     *a.nuniq = total;
@@ -1078,6 +1195,7 @@ __device__ void dedup_round(const RoundArgs &a, uint32_t s) {
     const uint32_t window = s < a.npods ? min(a.P, a.npods - s) : 0u;
     a.counters[2] -= window - total;
     a.counters[7] += window - total;
+    a.counters[CTR_CPU_SHARED] += shared;
   }
 }
 
@@ -1087,7 +1205,7 @@ __device__ __forceinline__ void advance_block(const RoundArgs &a) {
     advance_kernel_body(a);
     s_s = *a.sstart;
   }
-  if (a.rep == nullptr) return;
+  if (a.ulist == nullptr) return;
   __syncthreads();
   dedup_round(a, s_s);
 }

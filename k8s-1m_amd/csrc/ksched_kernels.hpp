@@ -13,6 +13,9 @@ constexpr int MAX_K = 512;    // candidates per pod record (two list entries per
 constexpr uint32_t FIX_NONE = 0xFFFFFFFFu;  // fix_list tail
 // device counters of the parallel commit (ksched_resolve.hip): chunk passes,
 // rounds it resolved
+// entries of cpu-sorted sweep lists whose cpu key equals their predecessor's
+// in the same pod group: the sweep keeps its cpu terms for them
+constexpr int CTR_CPU_SHARED = 9;
 constexpr int CTR_PAR_PASSES = 12, CTR_PAR_ROUNDS = 13, CTR_PAR_BAILS = 14, CTR_PAR_ONESTEP = 15;
 // per-pod round marks (ks_batch_marks, include/ksched.h): where the round
 // machinery changed course, for tests that place checks there
@@ -80,9 +83,16 @@ struct RoundArgs {
   // and the others read its record.  cls[i]: the batch index of pod i's
   // first identical pod (host); per round (by parity), written by the
   // advance kernel: rep[r] (the window's first pod of r's class), ulist
-  // (the representatives in window order) and nuniq (their count)
+  // (the representatives) and nuniq (their count).
+  // sort_cpu (every resource-only round, also one without identical pods,
+  // where cls and rep are null and each pod represents itself): ulist holds
+  // the representatives by cpu key (req_cpu, nz_cpu), then window index, so
+  // the sweep's per-node cpu terms serve a run of pods;
+  // otherwise ulist is in window order.  Everything after the sweep indexes
+  // by the pod's window index r, whatever the list's order.
   const uint32_t *cls;
   uint32_t *rep, *ulist, *nuniq;
+  uint32_t sort_cpu;
   BlockRec *brec;             // [local shards][P][bstride]
   uint64_t *srec;             // [S][P][rec_words(K)]
   uint64_t *frec;             // [P][rec_words(K)] (== srec when S == 1)
@@ -92,7 +102,8 @@ struct RoundArgs {
   const uint32_t *slot_pos;   // slot -> position
   uint64_t *counters;         // [0] rounds, [1] pods resolved, [2] pods swept, [3] wasted rounds,
                               // [4] FIX re-swept pods, [7] identical pods not swept (their class's
-                              // representative was; [2] counts representatives), [CTR_PAR_*]
+                              // representative was; [2] counts representatives), [CTR_CPU_SHARED],
+                              // [CTR_PAR_*]
   Weights w;
   FitParams fs;               // NodeResourcesFit strategy of the general kernel variants ...
   uint32_t fit_general;       // ... which the launchers choose when set (not {LeastAllocated, 1, 1}):

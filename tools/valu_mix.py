@@ -14,7 +14,11 @@ for ITS instruction mix, not a constant per instruction.  This tool:
      one inside it the pod loop, and what the outer loop holds besides is the
      batch step, which runs once per WL_T pods.  loop_valu is VALU per pod
      there: the pod loop's body (pod_valu) + the batch step's (batch_valu) /
-     WL_T, and the costs are weighted alike;
+     WL_T, and the costs are weighted alike.  The default strategy's
+     resource-only kernels recompute a node's cpu terms only where the pod's
+     cpu key changes: their pod loop is priced as the hit path (pod_valu) +
+     miss_rate x the cpu block (cpu_block_valu), with the miss rate a
+     parameter (--miss-rate, default MISS_RATE) recorded in the JSON;
   3. prices each opcode with the issue cost measured on MI355X at 4 waves per
      SIMD by tools/valu_issue.hip (profiles/valu_issue.jsonl); an opcode the
      microbenchmark does not cover takes its class's median (VOP1/VOP2
@@ -56,6 +60,10 @@ def bench_kernel_sources(root):
 KERNEL_SOURCES = bench_kernel_sources(ROOT)
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 HIPCC = "/opt/rocm/bin/hipcc"
+# Pods of a sweep block whose cpu key (req_cpu, nz_cpu) differs from the
+# previous pod's, per pod swept: they run the pod loop's cpu block.
+# 1 - ks_debug_counters [9] / [2] over a C3 run (bench.py --steps 20 --warmup 5)
+MISS_RATE = 0.345
 WAVES = 4  # the sweep's occupancy: 4 waves per SIMD (5 for the EXT kernels; the costs barely differ)
 FAST = re.compile(r"^v_(add|sub|subrev|and|or|xor|not|mov|ashrrev|lshrrev)_(u32|i32|b32|f32)(_e32|_e64)?$|"
                   r"^v_(add|mul)_f32(_e32)?$")
@@ -137,6 +145,59 @@ def pod_loop(ins, within=None):
     return best
 
 
+KEY_CMP = re.compile(r"^s_cmp_(eq|lg)_u64$")
+SGPR_PAIRS = re.compile(r"^s\[\d+:\d+\], s\[\d+:\d+\]$")
+COND = ("s_cbranch_vccz", "s_cbranch_vccnz", "s_cbranch_scc0", "s_cbranch_scc1")
+
+
+def branch_target(a, args):
+    off = int(re.match(r"^(-?\d+)", args).group(1))
+    return a + 4 + 4 * (off - 65536 if off >= 32768 else off)
+
+
+def cpu_block(ins, outer, inner):
+    """The pod loop's conditional block: the resource-only kernels
+    of the default strategy keep each node's cpu terms while the pod's cpu key
+    (req_cpu, nz_cpu) stays, and recompute them behind a wave-uniform branch on
+    a compare of two SGPR pairs.  One turn of the loop is walked from that
+    branch in both directions (other conditional branches fall through: they
+    leave the loop or skip a load; s_cbranch_exec* never jump, the wave is
+    whole), and the turn with fewer VALU instructions is the hit path.
+    Returns (hit addresses, miss-only addresses), or None without such a
+    branch (every other kernel)."""
+    body = [(a, op, args) for a, op, args in ins if inner[0] <= a < inner[1]]
+    # (a turn may re-enter a few scalar moves above the longest branch's target)
+    lo = min([inner[0]] + [branch_target(a, args) for a, op, args in body
+                           if op == "s_branch" and outer[0] <= branch_target(a, args)])
+    body = [(a, op, args) for a, op, args in ins if lo <= a < inner[1]]
+    at = {a: i for i, (a, _, _) in enumerate(body)}
+    key = None
+    for i, (a, op, args) in enumerate(body):
+        if KEY_CMP.match(op) and SGPR_PAIRS.match(args):
+            key = next((j for j in range(i + 1, len(body)) if body[j][1] in COND), None)
+            break
+    if key is None:
+        return None
+
+    def turn(taken):
+        seen, i = [], key
+        while True:
+            a, op, args = body[i]
+            if i == key and seen:
+                return seen
+            seen.append(a)
+            jump = op == "s_branch" or (i == key and taken)
+            nxt = at.get(branch_target(a, args)) if jump else i + 1
+            if nxt is None or nxt >= len(body) or len(seen) > len(body):
+                raise RuntimeError("the pod loop's turn leaves the loop")
+            i = nxt
+
+    valu = lambda path: sum(1 for a in path if body[at[a]][1].startswith("v_"))
+    p, q = turn(True), turn(False)
+    hit, miss = (p, q) if valu(p) <= valu(q) else (q, p)
+    return set(hit), set(miss) - set(hit)
+
+
 def general_variant(mangled: str) -> bool:
     """sweep_kernel<NPL, EXT, LWU, GF != 0>: the instances of a non-default
     NodeResourcesFit strategy, which bench.py never runs."""
@@ -169,6 +230,11 @@ def cost_of(op: str, costs: dict, fast_med: float, slow_med: float, args: str = 
 
 
 def main():
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--miss-rate", type=float, default=MISS_RATE,
+                    help="share of swept pods whose cpu key differs from their predecessor's")
+    miss_rate = ap.parse_args().miss_rate
     costs = load_costs(ROOT / "profiles" / "valu_issue.jsonl")
     fast = sorted(v for k, v in costs.items() if FAST.match(k))
     slow = sorted(v for k, v in costs.items() if not FAST.match(k) and v < 8)
@@ -183,11 +249,17 @@ def main():
         inner = pod_loop(ins, (lo, hi)) if batched else None
         if batched and inner is None:
             raise RuntimeError(f"{targs}: no pod loop inside the loop over the batches")
-        # (opcode, operands, weight): the batch step's instructions run once per T pods
-        loop = [(op, args, 1.0 if not batched or inner[0] <= a < inner[1] else 1.0 / T)
+        blk = cpu_block(ins, (lo, hi), inner) if batched else None
+        miss_only = blk[1] if blk else set()
+        # (opcode, operands, weight): the batch step's instructions run once per
+        # T pods, the cpu block's once per miss_rate pods
+        loop = [(op, args, miss_rate if a in miss_only else 1.0 if not batched or inner[0] <= a < inner[1] else 1.0 / T)
                 for a, op, args in ins if lo <= a < hi and op.startswith("v_")]
-        hist = collections.Counter(op for op, _, w in loop if w == 1.0)
-        bhist = collections.Counter(op for op, _, w in loop if w != 1.0)
+        in_batch = lambda a: batched and not (inner[0] <= a < inner[1])
+        hist = collections.Counter(op for a, op, _ in ins
+                                   if lo <= a < hi and op.startswith("v_") and not in_batch(a) and a not in miss_only)
+        mhist = collections.Counter(op for a, op, _ in ins if a in miss_only and op.startswith("v_"))
+        bhist = collections.Counter(op for a, op, _ in ins if lo <= a < hi and op.startswith("v_") and in_batch(a))
         n = sum(w for _, _, w in loop)
         cyc = covered = 0.0
         for op, args, w in loop:
@@ -200,11 +272,17 @@ def main():
         if batched:
             k.update(pod_valu=sum(hist.values()), batch_valu=sum(bhist.values()), batch_pods=T,
                      batch_hist=dict(bhist.most_common()))
+        if blk:
+            # pod_valu: the hit path; a pod whose cpu key differs from its
+            # predecessor's adds cpu_block_valu
+            k.update(cpu_block_valu=sum(mhist.values()), miss_rate=miss_rate, cpu_block_hist=dict(mhist.most_common()))
         res["kernels"][targs] = k
     out = ROOT / "profiles" / "valu_mix.json"
     out.write_text(json.dumps(res, indent=1) + "\n")
     for k, v in sorted(res["kernels"].items()):
         parts = f" = {v['pod_valu']} + {v['batch_valu']} / {v['batch_pods']}" if "pod_valu" in v else ""
+        if "cpu_block_valu" in v:
+            parts += f" + {v['miss_rate']} x {v['cpu_block_valu']}"
         print(f"sweep_kernel{k}: {v['loop_valu']}{parts} VALU per pod in the pod loop, {v['cycles_per_valu']} cycles each "
               f"(measured opcodes {v['measured_share']:.0%})")
     print("->", out.relative_to(ROOT))
