@@ -412,7 +412,14 @@ typedef struct {
   uint32_t world_size;       /* GPUs sharding the node index space (1 = no RCCL) */
   uint32_t rank;             /* this GPU's shard                                 */
   uint32_t virtual_shards;   /* >1: emulate that many shards on this one device  */
-  /* Score plugin weights (default profile: 1, 1, 3, 2, 1). */
+  /* Score plugin weights (default profile: 1, 1, 3, 2, 1).  ks_open accepts
+   * 0..10000 for each of them, weight_topology_spread,
+   * weight_inter_pod_affinity and hard_pod_affinity_weight included, and
+   * returns KS_ERR_INVALID outside.  A weight of 0 is taken as it stands: the
+   * plugin's normalised score is multiplied by 0 (a hard_pod_affinity_weight
+   * of 0 adds no score for existing pods' required affinity terms); the
+   * library does not replace it by the default.  What a configured 0 means
+   * upstream is for the caller to settle before it fills this struct. */
   int32_t weight_fit;        /* NodeResourcesFit                                */
   int32_t weight_balanced;   /* NodeResourcesBalancedAllocation                 */
   int32_t weight_taint;      /* TaintToleration                                 */

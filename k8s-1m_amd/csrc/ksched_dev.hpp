@@ -20,6 +20,10 @@ constexpr int BLOCK_KEYS = 4;   // candidates kept per sweep block and pod
 constexpr int MAX_SHARDS = 16;
 constexpr int MERGE_CAP = 4096; // candidates sorted per pod by the merge kernel
 constexpr uint64_t UNSCHED_BIT = 1ull << 63;  // hard-taint word: spec.unschedulable pseudo-taint
+// The largest score plugin weight (and hardPodAffinityWeight) ks_open accepts:
+// the bound the kernels' 24-bit multiplies and 32-bit sums are built on
+// (the sweep's key states its two claims beside KEY32_POS_BITS).
+constexpr int32_t KS_MAX_PLUGIN_WEIGHT = 10000;
 
 // Filter status codes (first failing plugin); FEASIBLE = passed every filter.
 constexpr int ST_FEASIBLE = -1;

@@ -3830,7 +3830,7 @@ ks_status ks_open(const ks_config *cfg, ks_ctx **out) {
   // weights are small non-negative integers (the kernels add them in 32 bits)
   for (int32_t w : {cfg->weight_fit, cfg->weight_balanced, cfg->weight_taint, cfg->weight_affinity, cfg->weight_image,
                     cfg->weight_topology_spread, cfg->weight_inter_pod_affinity, cfg->hard_pod_affinity_weight})
-    if (w < 0 || w > 10000) return KS_ERR_INVALID;
+    if (w < 0 || w > KS_MAX_PLUGIN_WEIGHT) return KS_ERR_INVALID;
   // percentageOfNodesToScore (ksched.h): below 100 on one GPU shard only
   if (cfg->percentage_of_nodes_to_score < 0 || cfg->percentage_of_nodes_to_score > 100) return KS_ERR_INVALID;
   if (cfg->percentage_of_nodes_to_score != 100 && c->S > 1) return KS_ERR_UNSUPPORTED;

@@ -182,6 +182,11 @@ __device__ __forceinline__ uint32_t normalize_inv(uint32_t raw, double inv) {
 // right guess (the usual case) one pass over the nodes suffices.
 // grid: x = block within shard, y = pod group, z = local shard.
 constexpr uint32_t KEY32_POS_BITS = 9, KEY32_POS_MASK = (1u << KEY32_POS_BITS) - 1;
+// a pre-shifted weight is a 24-bit operand of v_mad_u32_u24, and the key of the
+// largest TotalScore (four plugins at 100 under the largest weight) keeps its sign bit clear
+static_assert(((uint64_t)KS_MAX_PLUGIN_WEIGHT << KEY32_POS_BITS) < (1ull << 24), "pre-shifted weight: 24-bit operand");
+static_assert((((uint64_t)4 * 100 * KS_MAX_PLUGIN_WEIGHT + 1) << KEY32_POS_BITS) + KEY32_POS_MASK < (1ull << 31),
+              "the sweep's 32-bit key");
 
 // GF: the NodeResourcesFit score under the context's strategy (score_fit,
 // a.fs) instead of {LeastAllocated, 1, 1}: 1 LeastAllocated / MostAllocated

@@ -169,8 +169,11 @@ class Scheduler:
                  weights: Optional[Dict[str, int]] = None, options: Optional[Dict[str, int]] = None,
                  percentage_of_nodes_to_score: int = 100, fit_strategy: str = "LeastAllocated",
                  fit_resource_weights: Optional[Dict[str, int]] = None, fit_shape=None,
-                 balanced_resources=None):
-        """options: ks_config execution options by field name (_abi.OPTION_FIELDS),
+                 balanced_resources=None, hard_pod_affinity_weight: int = 1):
+        """weights: the profile's score plugin weights by plugin name, over
+        DEFAULT_WEIGHTS.  hard_pod_affinity_weight: InterPodAffinityArgs.
+        hardPodAffinityWeight.  A weight of 0 multiplies by 0 (ksched.h).
+        options: ks_config execution options by field name (_abi.OPTION_FIELDS),
         e.g. {"resolve_mode": _abi.RESOLVE_SERIAL, "dedup_identical_pods": 0};
         none of them changes a result.  percentage_of_nodes_to_score: the
         profile's percentageOfNodesToScore (ksched.h; below 100 one shard only).
@@ -201,7 +204,7 @@ class Scheduler:
         cfg.weight_image = w["ImageLocality"]
         cfg.weight_topology_spread = w["PodTopologySpread"]
         cfg.weight_inter_pod_affinity = w["InterPodAffinity"]
-        cfg.hard_pod_affinity_weight = 1
+        cfg.hard_pod_affinity_weight = hard_pod_affinity_weight
         cfg.percentage_of_nodes_to_score = percentage_of_nodes_to_score
         self.weights = w
         self.capacity = node_capacity

@@ -82,10 +82,16 @@ def lib() -> C.CDLL:
 
 class Oracle:
     def __init__(self, capacity: int, weights=(1, 1, 3, 2, 1, 2), threads: int = 1, percentage: int = 100):
+        """weights: (fit, balanced, taint, affinity, image[, spread[,
+        InterPodAffinity[, hardPodAffinityWeight]]]); what is left out keeps
+        its default (2, 2, 1)."""
         self.L = lib()
+        assert 5 <= len(weights) <= 8, weights
         self.o = self.L.oracle_new(capacity, *weights[:5])
         if len(weights) > 5:
             self.L.oracle_set_weight_spread(self.o, weights[5])
+        if len(weights) > 6:
+            self.L.oracle_set_weight_inter_pod_affinity(self.o, weights[6], weights[7] if len(weights) > 7 else 1)
         self.capacity = capacity
         if threads > 1:
             self.L.oracle_set_threads(self.o, threads)

@@ -10,6 +10,28 @@ RES_DT = np.dtype([("node_index", "<i4"), ("status", "<i4"), ("total_score", "<i
                    ("evaluated", "<u4"), ("fail", "<u4", (8,)), ("flags", "<u4"), ("_pad", "<u4")])
 
 
+# The profile's score plugin weights as a tuple: the order of pyoracle.Oracle's
+# weights (and of ks_config's fields), then hardPodAffinityWeight.
+WEIGHT_PLUGINS = ("NodeResourcesFit", "NodeResourcesBalancedAllocation", "TaintToleration", "NodeAffinity",
+                  "ImageLocality", "PodTopologySpread", "InterPodAffinity")
+DEFAULT_VECTOR = (1, 1, 3, 2, 1, 2, 2, 1)
+
+
+def weight_forms(vec):
+    """A weight vector (fit, balanced, taint, affinity, image, spread, ipa,
+    hard) in both forms: Scheduler's keyword arguments and pyoracle.Oracle's
+    weights tuple."""
+    vec = tuple(int(v) for v in vec)
+    assert len(vec) == 8, vec
+    return dict(weights=dict(zip(WEIGHT_PLUGINS, vec[:7])), hard_pod_affinity_weight=vec[7]), vec
+
+
+def oracle_weights(weights=None, hard=1):
+    """Scheduler's weights dict (over the defaults) and hardPodAffinityWeight as pyoracle.Oracle's tuple."""
+    w = dict(zip(WEIGHT_PLUGINS, DEFAULT_VECTOR[:7]), **(weights or {}))
+    return tuple(int(w[p]) for p in WEIGHT_PLUGINS) + (int(hard),)
+
+
 def res_array(raw, n):
     return np.frombuffer(C.string_at(C.addressof(raw), n * C.sizeof(_abi.KsResult)), dtype=RES_DT).copy()
 

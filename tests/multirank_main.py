@@ -23,13 +23,15 @@ for p in ("k8s-1m_amd", "oracle", "tests"):
 import numpy as np  # noqa: E402
 
 import pyoracle  # noqa: E402
-from helpers import res_array, state_array  # noqa: E402
+from helpers import DEFAULT_VECTOR, res_array, state_array, weight_forms  # noqa: E402
 from ksched import Scheduler, synth  # noqa: E402
 
 
 def main(cfg):
     world, kind, n, m = cfg["world"], cfg["kind"], cfg["nodes"], cfg["pods"]
     P, K, calls = cfg.get("P", 256), cfg.get("K", 0), cfg.get("calls", 3)
+    # "weights": the profile's plugin weights as a vector (helpers.weight_forms), on every context and the oracle
+    wkw, wvec = weight_forms(cfg.get("weights") or DEFAULT_VECTOR)
     nodes = synth.nodes(kind, n, cfg.get("node_seed", 11))
     slots = synth.slot_array(n)
     if cfg.get("pods_kind") in ("spread", "affinity"):
@@ -42,9 +44,9 @@ def main(cfg):
     else:
         pods = synth.pods(kind, m, cfg.get("pod_seed", 12))
     pre = synth.prefill(kind, n, 1, 3, 0.5) if cfg.get("prefill") else None
-    ranks = [Scheduler(n, device=0, pods_per_round=P, topk=K, world_size=world, rank=r) for r in range(world)]
+    ranks = [Scheduler(n, device=0, pods_per_round=P, topk=K, world_size=world, rank=r, **wkw) for r in range(world)]
     Scheduler.comm_init_local(ranks)
-    one = Scheduler(n, device=0, pods_per_round=P, topk=K)
+    one = Scheduler(n, device=0, pods_per_round=P, topk=K, **wkw)
     for s in ranks + [one]:
         s.upsert_nodes_raw(nodes.nodes, slots, n)
         if pre is not None:
@@ -75,7 +77,7 @@ def main(cfg):
         return {"ok": False, "error": "; ".join(errs)}
     want_one = np.concatenate([res_array(one.schedule_raw(pods.pods_at(cuts[i]), cuts[i + 1] - cuts[i]),
                                          cuts[i + 1] - cuts[i]) for i in range(calls)])
-    o = pyoracle.Oracle(n, threads=16)
+    o = pyoracle.Oracle(n, wvec, threads=16)
     o.upsert(nodes.nodes, slots, n)
     if pre is not None:
         o.add_pods(pre.pods, pre.slot_ptr, pre.n_pods)

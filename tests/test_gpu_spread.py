@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import pyoracle
-from helpers import assert_results_equal, res_array, scores_array, states_np
+from helpers import assert_results_equal, oracle_weights, res_array, scores_array, states_np
 from ksched import Scheduler, _abi
 from ksched.objects import (Arena, Container, LabelSelector, LabelSelectorRequirement, Node, Pod, Taint,
                             Toleration, TopologySpreadConstraint as TSC, nodes_array, pods_array,
@@ -39,7 +39,8 @@ class Pair:
         self.n = n
         self.a = Arena()
         self.s = Scheduler(n, **cfg)
-        self.o = pyoracle.Oracle(n)
+        # the profile's plugin weights, when the configuration carries any, go to both
+        self.o = pyoracle.Oracle(n, oracle_weights(cfg.get("weights"), cfg.get("hard_pod_affinity_weight", 1)))
 
     def upsert(self, nodes, slots):
         na, k = nodes_array(nodes, self.a)
