@@ -592,6 +592,46 @@ void ks_batch_free(ks_ctx *ctx, ks_batch *batch);
 ks_status ks_batch_submit(ks_ctx *ctx, ks_batch *batch);
 ks_status ks_batch_wait(ks_ctx *ctx, ks_batch *batch);
 
+/* Cache.ForgetPod for pods this batch placed. idx[0..n) are indices into the
+ * batch (strictly increasing). *skipped may be null.
+ *
+ * The cache afterwards equals the cache after ks_pods_remove(ctx, pods[idx],
+ * slots = results[idx].node_index, n): Requested, NonZeroRequested and the pod
+ * count, Requested of every extended-resource column the pod requests, the
+ * node's used-port bits (cleared outright, as HostPortInfo.Remove does), the
+ * selector-class and term-class counts and the per-node pod records -- for
+ * every kind of pod a batch schedules.  The call takes no ks_pod: what the
+ * commit wrote is taken back from the compiled batch, which stays resident
+ * until ks_batch_free; the index list is the only upload.  ks_pods_remove
+ * remains the call for pods bound by someone else.
+ *
+ * As every other call it first waits for all submitted batches.  The batch
+ * must have run (ks_batch_run returned KS_OK or ks_batch_wait did) and not be
+ * freed; ks_batch_results stays valid and unchanged.  Nothing is applied
+ * unless the whole list is valid: KS_ERR_INVALID, with ks_last_error naming
+ * the first offender, for a null ctx or batch, null idx with n > 0, a batch
+ * that has not run, an index >= the batch's pod count, a list not strictly
+ * increasing, an index whose result is not KS_POD_SCHEDULED, and an index
+ * already forgotten since the batch's last run (a new run of the batch places
+ * every pod anew and clears that record).  n == 0 is KS_OK.
+ *
+ * As upstream's ForgetPod, the call tolerates a node that is gone: a pod whose
+ * slot was deleted since the batch ran -- or deleted and filled with a new
+ * node -- is skipped and counted in *skipped, never subtracted from another
+ * node's row (it counts as forgotten all the same).  A node upserted in place
+ * keeps its pods, so such a pod is forgotten normally.  nextStartNodeIndex,
+ * the scoring strategy, the balanced list and the interned dictionaries are
+ * untouched; host-port triples are never freed.  With several ranks every
+ * rank makes the same call, as for ks_pods_remove. */
+ks_status ks_batch_forget(ks_ctx *ctx, ks_batch *batch, const uint32_t *idx, uint32_t n, uint32_t *skipped);
+/* last ks_batch_forget: [0] pods taken back, [1] pods skipped (node gone),
+ * [2] of [0] those with a one-pod program (SoloHdr), [3] launches of the
+ * forget kernel, [4..7] 0.  Host only.  ([4] is the kernel's own count of
+ * pods one of its bound checks turned away; it stays 0 unless the batch's
+ * resident data and the host's copy of its results disagree, and the call
+ * that finds it non-zero fails with KS_ERR_DEVICE.) */
+ks_status ks_debug_forget(ks_ctx *ctx, uint64_t out[8]);
+
 /* Per-plugin scores of `pod` on every node slot against the current cache
  * (out has node_capacity entries).  Parity dump of NodePluginScores. */
 ks_status ks_plugin_scores(ks_ctx *ctx, const ks_pod *pod, ks_node_score *out);

@@ -39,6 +39,7 @@
 #include "ksched_dev.hpp"
 #include "ksched_diag.hpp"
 #include "ksched_explain.hpp"
+#include "ksched_forget.hpp"
 #include "ksched_kernels.hpp"
 #include "ksched_sync.hpp"
 
@@ -356,6 +357,10 @@ struct ks_batch {
   // byte-identical descriptor; dups = some pod repeats an earlier one
   uint32_t *d_cls = nullptr, *h_cls = nullptr;
   bool dups = false;
+  // ks_batch_forget: ran = the last run placed its pods (their
+  // records are resident and logged); the pods taken back since that run
+  bool ran = false;
+  ForgetBits forgotten;
   // asynchronous run state (ks_batch_submit / ks_batch_wait)
   bool queued = false, done = false;
   ks_status run_status = KS_OK;
@@ -494,6 +499,11 @@ struct ks_ctx {
   std::vector<HostNode> nodes;
   uint32_t n_present = 0;
   std::vector<uint8_t> present_map;  // HostNode::present by slot, compact (pod events check it per pod)
+  // runs_started when the slot was last reset (its node deleted, or a node put into the empty slot):
+  // a batch whose run_seq is not above it bound its pods there to a node that has left (ks_batch_forget)
+  std::vector<uint64_t> slot_reset;
+  uint64_t last_reset = 0;  // the largest entry: a batch run after it has lost no node
+  uint64_t forget_ctr[8] = {};  // the last ks_batch_forget (ks_debug_forget)
   // ks_snapshot_update: the last NodeInfo.Generation applied per slot, and the max
   std::vector<int64_t> slot_gen;
   int64_t snapshot_gen = 0;
@@ -3407,6 +3417,7 @@ ks_status batch_acquire(ks_ctx *c, uint32_t n, size_t words, ks_batch **out) {
   }
   b->n = 0;
   b->queued = b->done = false;
+  b->ran = false;
   b->run_status = KS_OK;
   b->run_err.clear();
   *out = b;
@@ -3584,6 +3595,8 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
     if ((st0 = upload_dirty_ext(c, c->xm))) return st0;
     c->run_t = c->t;
     b->run_seq = ++c->runs_started;
+    b->ran = false;
+    b->forgotten.reset(b->n);  // every pod is placed anew
     b->cmask_epoch = c->class_epoch;
     for (int k = 0; k < MAX_CLASSES; ++k) {
       classes |= c->classes[k].live;
@@ -3733,6 +3746,7 @@ ks_status run_batch(ks_ctx *c, ks_batch *b) {
     // any later batch runs on the stream
     if (ks_status st = late_class_counts(c, b)) return st;
     c->runs_done = b->run_seq;
+    b->ran = true;
   }
   if (c->timing) {
     PhaseTimer rd(c, PROF_TIMING);
@@ -3950,6 +3964,7 @@ static ks_status open_device(ks_ctx *x, const ks_config *cfg) {
     for (uint32_t l = 0; l < sh.count; ++l) x->slot_pos[sh.lo + l] = shard_pos(sh, x->npl, l);
   x->nodes.resize(x->cap);
   x->present_map.assign(x->cap, 0);
+  x->slot_reset.assign(x->cap, 0);
   // device table
   ks_status st;
   NodeTable &t = x->t;
@@ -4156,6 +4171,7 @@ ks_status ks_nodes_upsert(ks_ctx *c, const ks_node *nodes, const uint32_t *slots
       node_images_ref(c, h, -1);
     } else {
       c->n_present++;
+      c->slot_reset[slot] = c->last_reset = c->runs_started;
     }
     h.present = true;
     c->present_map[slot] = 1;
@@ -4360,6 +4376,7 @@ ks_status ks_nodes_delete(ks_ctx *c, const uint32_t *slots, uint32_t n) {
     node_images_ref(c, h, -1);
     h = HostNode();
     c->present_map[slots[i]] = 0;
+    c->slot_reset[slots[i]] = c->last_reset = c->runs_started;
     c->n_present--;
     pos[i] = c->slot_pos[slots[i]];
     core[(size_t)i * 8 + 2] = -1;  // apods < 0: empty slot
@@ -4867,6 +4884,87 @@ void ks_batch_free(ks_ctx *c, ks_batch *b) {
     b->term_refs.clear();
   }
   batch_release(c, b);
+}
+
+// Cache.ForgetPod for pods the batch placed: the inverse of
+// the commits that placed them, from what the batch still holds -- no ks_pod,
+// no host compile; the index list is the only upload.
+ks_status ks_batch_forget(ks_ctx *c, ks_batch *b, const uint32_t *idx, uint32_t n, uint32_t *skipped) {
+  if (!c) return KS_ERR_INVALID;
+  if (!b) return c->fail(KS_ERR_INVALID, "ks_batch_forget: no batch");
+  if (n && !idx) return c->fail(KS_ERR_INVALID, "ks_batch_forget: no index list for %u pods", n);
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  if (!b->ran) return c->fail(KS_ERR_INVALID, "ks_batch_forget: the batch has not run");
+  // the whole list before anything changes
+  const ForgetListCheck chk = forget_check_list(idx, n, b->n, b->forgotten, [&](uint32_t i) {
+    return b->h_results[i].status == KS_POD_SCHEDULED && (uint32_t)b->h_results[i].node_index < c->cap;
+  });
+  if (chk.err) return c->fail(KS_ERR_INVALID, "%s", forget_list_message(chk, idx, b->n).c_str());
+  std::memset(c->forget_ctr, 0, sizeof c->forget_ctr);
+  if (skipped) *skipped = 0;
+  if (!n) return KS_OK;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  // pods whose node left since the run (deleted, or deleted and the slot filled again) are skipped:
+  // the row they were counted in is gone, and the slot's new row never held them
+  std::vector<uint32_t> keep, slots, sets;
+  keep.reserve(n);
+  slots.reserve(n);
+  sets.reserve(n);
+  uint64_t solo = 0;
+  const bool lost_nodes = c->last_reset >= b->run_seq;  // else no slot was reset since the run: no per-slot look-up
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t i = idx[k], slot = (uint32_t)b->h_results[i].node_index;
+    if (lost_nodes && c->slot_reset[slot] >= b->run_seq) continue;
+    keep.push_back(i);
+    slots.push_back(slot);
+    sets.push_back(b->set_ids[i]);
+    solo += (b->h_pods[i].flags & PF_SOLO) != 0;
+  }
+  const uint32_t m = (uint32_t)keep.size();
+  uint32_t missed = 0;
+  if (m) {
+    // the list and, behind it, the kernel's count of pods it turned away (zero going up)
+    keep.push_back(0);
+    const size_t bytes = ((size_t)m + 1) * 4 + 1024;
+    ks_status st = xfer_begin(c, bytes, bytes);
+    if (st) return st;
+    uint32_t *d_idx = dscratch<uint32_t>(c, (size_t)m + 1);
+    if ((st = h2d(c, d_idx, keep.data(), ((size_t)m + 1) * 4))) return st;
+    ForgetArgs fa{};
+    fa.t = c->t;
+    fa.slot_pos = c->d_slot_pos;
+    fa.results = b->d_results;
+    fa.pods = b->d_pods;
+    fa.clauses = b->d_clauses;
+    fa.idx = d_idx;
+    fa.xreq = c->d_xreq;
+    fa.used_ports = c->d_used_ports;
+    fa.n_words = b->n_words;
+    fa.n = m;
+    fa.npods = b->n;
+    fa.nslots = c->cap;
+    fa.missed = d_idx + m;
+    HIPC(c, launch_forget(fa, c->stream));
+    c->forget_ctr[3] = 1;
+    if ((st = d2h(c, &missed, d_idx + m, 4)) || (st = xfer_sync(c))) return st;
+    c->forget_ctr[4] = missed;
+  }
+  for (uint32_t k = 0; k < n; ++k) b->forgotten.set(idx[k]);  // a skipped pod is forgotten too (its node took it along)
+  c->forget_ctr[0] = m;
+  c->forget_ctr[1] = n - m;
+  c->forget_ctr[2] = solo;
+  if (skipped) *skipped = n - m;
+  if (missed)  // the batch's resident data and the host's copy of its results disagree
+    return c->fail(KS_ERR_DEVICE, "ks_batch_forget: the kernel turned %u of %u pods away", missed, m);
+  if (!m) return KS_OK;
+  // selector-class and term-class columns, the log of bound pods, the host records
+  return spread_pods_delta(c, sets.data(), slots.data(), m, -1);
+}
+
+ks_status ks_debug_forget(ks_ctx *c, uint64_t out[8]) {
+  if (!c || !out) return KS_ERR_INVALID;
+  std::memcpy(out, c->forget_ctr, sizeof c->forget_ctr);
+  return KS_OK;
 }
 
 ks_status ks_schedule(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_result *out) {

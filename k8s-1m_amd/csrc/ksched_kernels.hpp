@@ -358,6 +358,28 @@ hipError_t launch_gather_rows(const NodeTable &t, const uint32_t *pos, int64_t *
 hipError_t launch_scatter_u64(uint64_t *col, const uint32_t *pos, const uint64_t *val, uint32_t n,
                               hipStream_t st);
 hipError_t launch_dump(const DumpArgs &a, hipStream_t st);
+// ks_batch_forget (ksched_forget.hip): the pods idx[0..n) of a
+// batch that ran, taken back from the rows they were bound to: Requested,
+// NonZeroRequested and the pod count from the PodDev, the extended-resource
+// columns and the used-port bits from the pod's SoloHdr.  One lane per pod,
+// atomics throughout (pods of one call share nodes).  xreq / used_ports may be
+// null (no column / no dictionary entry yet: no pod of the batch has either).
+struct ForgetArgs {
+  NodeTable t;
+  const uint32_t *slot_pos;  // [nslots]
+  const DevResult *results;  // the batch's, [npods]
+  const PodDev *pods;        // [npods]
+  const uint64_t *clauses;   // the batch's clause buffer, n_words words
+  const uint32_t *idx;       // [n] batch indices
+  int64_t *xreq;             // [MAX_XRES][npos]
+  uint64_t *used_ports;      // [npos]
+  uint32_t *missed;          // += pods a bound check of the kernel turned away (zeroed by the caller; 0 unless
+                             // host and device disagree)
+  uint64_t n_words;
+  uint32_t n, npods, nslots;
+};
+constexpr uint32_t FORGET_THREADS = 256;
+hipError_t launch_forget(const ForgetArgs &a, hipStream_t st);
 // ks_debug_stall: one wave that waits `usec` microseconds of wall clock, then exits
 hipError_t launch_stall(uint32_t usec, hipStream_t st);
 

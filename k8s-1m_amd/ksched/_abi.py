@@ -389,6 +389,7 @@ KSCHED_SYMBOLS = [
     "ks_diagnose", "ks_fit_error_message",
     "ks_diagnose_pods", "ks_debug_diagnose_pods",
     "ks_explain",
+    "ks_batch_forget", "ks_debug_forget",
 ]
 KSGATHER_SYMBOLS = [
     "ksg_open", "ksg_close", "ksg_set_members", "ksg_record_and_wait", "ksg_pending", "ksg_fnv1_32", "ksg_target_index",
@@ -450,6 +451,8 @@ def ksched_lib() -> C.CDLL:
     L.ks_batch_free.restype = None
     L.ks_batch_submit.argtypes = [vp, vp]
     L.ks_batch_wait.argtypes = [vp, vp]
+    L.ks_batch_forget.argtypes = [vp, vp, P(C.c_uint32), C.c_uint32, P(C.c_uint32)]
+    L.ks_debug_forget.argtypes = [vp, P(C.c_uint64)]
     L.ks_pods_check.argtypes = [vp, P(KsPod), C.c_uint32, P(C.c_int32)]
     L.ks_plugin_scores.argtypes = [vp, P(KsPod), P(KsNodeScore)]
     L.ks_node_states.argtypes = [vp, P(C.c_uint32), C.c_uint32, P(KsNodeState)]

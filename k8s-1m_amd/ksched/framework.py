@@ -588,6 +588,29 @@ class Scheduler:
         self._ok(self.lib.ks_batch_marks(self.ctx, batch, out))
         return bytes(out)[:n]
 
+    def forget(self, batch, indices: Sequence[int]) -> int:
+        """Cache.ForgetPod for pods ``batch`` placed (ks_batch_forget): ``indices``
+        are batch indices, strictly increasing (a numpy uint32 array is passed
+        as it is).  Returns how many were skipped because their node has left
+        since the batch ran."""
+        n = len(indices)
+        if hasattr(indices, "ctypes"):  # a numpy array
+            arr = indices.astype("uint32", order="C", copy=False)
+            ptr = arr.ctypes.data_as(C.POINTER(C.c_uint32))
+        else:
+            arr = (C.c_uint32 * max(1, n))(*indices)
+            ptr = arr
+        skipped = C.c_uint32()
+        self._ok(self.lib.ks_batch_forget(self.ctx, batch, ptr, n, C.byref(skipped)))
+        return int(skipped.value)
+
+    def forget_counters(self) -> List[int]:
+        """ks_debug_forget: the last ``forget`` ([0] pods taken back, [1] skipped,
+        [2] of [0] with a one-pod program, [3] launches of the forget kernel)."""
+        out = (C.c_uint64 * 8)()
+        self._ok(self.lib.ks_debug_forget(self.ctx, out))
+        return [int(v) for v in out]
+
     def free(self, batch):
         self.lib.ks_batch_free(self.ctx, batch)
 
