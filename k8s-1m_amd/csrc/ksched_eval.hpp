@@ -389,6 +389,12 @@ __device__ __forceinline__ int32_t score_ba_sum(double sc, double sm, const Node
 __device__ __forceinline__ double ba_fraction(double s, double alloc, double inv) {
   return fmin(div_rn(s, alloc, inv), 1.0);
 }
+// The fraction in two steps, for the sweep that clamps only where the clamp
+// can act: ba_clamp(ba_quotient(..)) is ba_fraction(..), and
+// where s <= alloc -- the fit check of a non-zero request on the same exact
+// sums -- the quotient is already at most 1 (0 for alloc == 0, inv == 0).
+__device__ __forceinline__ double ba_quotient(double s, double alloc, double inv) { return div_rn(s, alloc, inv); }
+__device__ __forceinline__ double ba_clamp(double q) { return fmin(q, 1.0); }
 // BalancedAllocation from the two fractions (f0 cpu, f1 memory)
 __device__ __forceinline__ int32_t score_ba_fractions(double f0, double f1, const NodeRegs &r) {
   const double om = __builtin_fma(-fabs(f0 - f1), r.bamul, 1.0);

@@ -40,28 +40,30 @@ namespace ks {
 
 
 
-// A wave-uniform pod descriptor.  SCALAR (the resource-only sweep): through
-// the constant address space, i.e. s_load into SGPRs -- the generic pointer
-// gave three vector loads per pod and a compare + readfirstlane per request
-// test (round 5: C3 sweep 0.358 -> 0.355 ms).  The EXT sweep keeps the
-// generic load (the copy took 48 B of scratch there).  Batches are never
-// written while kernels read them.
+// A wave-uniform pod descriptor for the resource-only sweep: through the
+// constant address space, i.e. s_load into SGPRs -- the generic pointer gave
+// three vector loads per pod and a compare + readfirstlane per request test
+// (round 5: C3 sweep 0.358 -> 0.355 ms).  Batches are never written while
+// kernels read them.
+// Only the four binary64 fields are loaded (one 32-byte load), the others stay
+// zero: a resource-only pod is evaluated by them alone -- req_cpu_d / req_mem_d
+// are the requests exactly, +0.0 the zero request -- and the descriptor is
+// fetched a pod ahead, where a register that a load in flight will write but
+// nobody reads is a register the compiler hands out as a temporary, behind a
+// wait for that load.
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) u32x4 *const_words;
-template <bool SCALAR = false>
-__device__ __forceinline__ PodDev load_pod(const PodDev *pods, uint32_t i) {
-  if constexpr (SCALAR) {
-    const const_words src = (const_words)(pods + i);
-    u32x4 w[sizeof(PodDev) / 16];
-#pragma unroll
-    for (int k = 0; k < (int)(sizeof(PodDev) / 16); ++k) w[k] = src[k];
-    PodDev p;
-    __builtin_memcpy(&p, w, sizeof p);
-    return p;
-  } else {
-    return pods[i];
-  }
+__device__ __forceinline__ PodDev load_pod_requests(const PodDev *pods, uint32_t i) {
+  static_assert(offsetof(PodDev, req_cpu_d) == 32 && offsetof(PodDev, nz100_cpu) == 48 &&
+                offsetof(PodDev, tol_hard) == 64, "PodDev: the binary64 request fields");
+  const const_words src = (const_words)(pods + i);
+  const u32x4 w2 = src[2], w3 = src[3];
+  PodDev p = {};
+  __builtin_memcpy(&p.req_cpu_d, &w2, 16);
+  __builtin_memcpy(&p.nz100_cpu, &w3, 16);
+  return p;
 }
+__device__ __forceinline__ uint64_t f64_bits(double x) { return (uint64_t)__double_as_longlong(x); }
 
 
 // The value stays in one VGPR (pair) from here on: an empty asm the compiler
@@ -197,7 +199,7 @@ template <int NPL, bool EXT, int LWU = LW, int GF = 0>
 // 5 % faster than 4 (103 VGPRs); 6 waves spill 72 B; the resource-only
 // kernel at 5 waves spills 20 B and measured 9 % slower (kept at 4).  The
 // general variants keep 4 waves (at 5 the scorer's registers spill up to 60 B)
-__global__ __launch_bounds__(SWEEP_THREADS) __attribute__((amdgpu_waves_per_eu(EXT && NPL == 2 && !GF ? 5 : 1)))
+__global__ __launch_bounds__(SWEEP_THREADS) __attribute__((amdgpu_waves_per_eu(EXT ? (NPL == 2 && !GF ? 5 : 1) : NPL == 8 ? 2 : NPL == 4 && !GF ? 4 : 1)))
 void sweep_kernel(RoundArgs a) {
   static_assert(NPL * WAVE <= (1 << KEY32_POS_BITS), "wave-local key position field");
   constexpr int NW = SWEEP_THREADS / WAVE;
@@ -271,19 +273,21 @@ void sweep_kernel(RoundArgs a) {
   // pod count and cpu fit -- are kept across pods and batches and recomputed
   // only where the key changes (wave-uniform: the pod sits in SGPRs).
   // Requests are >= 0, so -1 matches no pod: a block's first pod recomputes.
+  // The key is held and compared as the bit patterns of (req_cpu_d, nz100_cpu),
+  // the pair's exact binary64 copies (compile_pod: integers in [0, 2^46), and
+  // x 100 below 2^53): equal patterns are equal pairs and the other way
+  // round, 0 is the zero request, and all-ones is a NaN that no pod carries.
+  // So the body reads the descriptor's four doubles alone, one 32-byte load.
   constexpr bool SHARE = !EXT && GF == 0;
-  int64_t ck_req = -1, ck_nz = -1;
+  uint64_t ck_req = ~0ull, ck_nz = ~0ull;
   double c_f0[SHARE ? NPL : 1];
   int32_t c_la[SHARE ? NPL : 1];
   uint64_t c_fm[SHARE ? NPL : 1];  // SGPR pairs
   static_for<(SHARE ? NPL : 1)>([&](auto J) { c_f0[J] = 0.0; c_la[J] = 0; c_fm[J] = 0; });
-  // One pod (q: its place in the batch, resource-only kernels)
-  auto sweep_pod = [&](const uint32_t it, const uint32_t q) __attribute__((always_inline)) {
-    // FIX mode: slice entry it - start of the compacted flagged-pod list
-    const uint32_t r = fix ? uniform_u32(a.fix_list[it - start]) : dedup ? uniform_u32(a.ulist[it - start]) : it - start;
-    if (fix && r == FIX_NONE) return;
-    const uint32_t pi = start + r;
-    const PodDev p = load_pod<!EXT>(a.pods, pi);
+  // One pod with its descriptor p.  r: its list entry (label / taint kernels);
+  // q: its place in the batch (resource-only kernels, whose loop below fetches
+  // the entries and the descriptors ahead)
+  auto sweep_pod = [&](const uint32_t it, const uint32_t q, const uint32_t r, const PodDev &p) __attribute__((always_inline)) {
     uint32_t tt_max = 0, na_max = 0;
     if (EXT && (p.flags & (PF_TT | PF_NA))) {
       tt_max = uniform_u32(fix ? a.norm_max[2 * r + 0] : p.tt_guess);
@@ -305,36 +309,65 @@ void sweep_kernel(RoundArgs a) {
       // divides (exact integers in binary64), so the free columns need no
       // registers; a zero request's check is masked off (all-ones lane mask)
       // (lane masks of the wave-uniform conditions: SGPR pairs)
-      const uint64_t zc = __builtin_amdgcn_ballot_w64(p.req_cpu == 0), zm = __builtin_amdgcn_ballot_w64(p.req_mem == 0);
+      uint64_t zc, zm;
+      // (the requests and the cpu key as the bit patterns of their exact
+      // binary64 copies: load_pod_requests)
+      const uint64_t rq_cpu = f64_bits(p.req_cpu_d), rq_mem = f64_bits(p.req_mem_d), nz_cpu = f64_bits(p.nz100_cpu);
+      if constexpr (SHARE) {  // the pod sits in SGPRs: all-ones / zero by scalar selects, no lane compare
+        zc = uniform_zero_mask(rq_cpu);
+        zm = uniform_zero_mask(rq_mem);
+      } else {
+        zc = __builtin_amdgcn_ballot_w64(rq_cpu == 0);
+        zm = __builtin_amdgcn_ballot_w64(rq_mem == 0);
+      }
       if constexpr (SHARE) {
         // the key is the pair: a container without a cpu request makes
         // nz_cpu differ between pods of one req_cpu
-        if (p.req_cpu != ck_req || p.nz_cpu != ck_nz) {
-          ck_req = p.req_cpu;
-          ck_nz = p.nz_cpu;
+        if (rq_cpu != ck_req || nz_cpu != ck_nz) {
+          ck_req = rq_cpu;
+          ck_nz = nz_cpu;
           static_for<NPL>([&](auto J) {
             constexpr int j = J;
             const double sc = nr[j].rcpu + p.req_cpu_d;
             c_fm[j] = podfit_m[j] & (zc | __builtin_amdgcn_ballot_w64(!(sc > nr[j].acpu_d)));
             c_la[j] = least_requested(nr[j].lf100_cpu, p.nz100_cpu, nr[j].inv_cpu);
-            c_f0[j] = ba_fraction(sc, nr[j].acpu_d, nr[j].inv_cpu);
+            c_f0[j] = ba_quotient(sc, nr[j].acpu_d, nr[j].inv_cpu);
           });
+          // min(1, .) only where a lane that keeps its key can exceed 1: a
+          // zero request (ba_quotient).  The key (req_cpu, nz_cpu) separates a
+          // zero-request pod from every other, so kept fractions never cross
+          if (rq_cpu == 0) {
+            static_for<NPL>([&](auto J) { c_f0[J] = ba_clamp(c_f0[J]); });
+            asm volatile("");  // (stays a branch, as below)
+          }
         }
         // one register per kept value on both paths: without this the
         // compiler rotates the pod loop and copies all of them on every pod
         static_for<NPL>([&](auto J) { pin_vgpr(c_f0[J]); pin_vgpr(c_la[J]); });
         // the memory side and the joint part, as score_la / score_ba_sum and
         // the key build below compute them
+        // (the memory fractions of the lane's nodes wait for one clamp under
+        // one branch; the empty asm keeps it a branch: as a select it is the
+        // clamp and two moves more per node)
+        double f1[NPL];
+        uint64_t fm[NPL];  // SGPR pairs
         static_for<NPL>([&](auto J) {
           constexpr int j = J;
           const double sm = nr[j].rmem + p.req_mem_d;
-          const uint64_t fm = c_fm[j] & (zm | __builtin_amdgcn_ballot_w64(!(sm > nr[j].amem_d)));
-          const double f1 = ba_fraction(sm, nr[j].amem_d, nr[j].inv_mem);
-          const uint32_t key = sel_mask(fm, wmad_s(wf9, (uint32_t)score_la_cpu(c_la[j], p.nz100_mem, nr[j]),
-                                                   wmad_s(wb9, (uint32_t)score_ba_fractions(c_f0[j], f1, nr[j]), kc[j])));
+          fm[j] = c_fm[j] & (zm | __builtin_amdgcn_ballot_w64(!(sm > nr[j].amem_d)));
+          f1[j] = ba_quotient(sm, nr[j].amem_d, nr[j].inv_mem);
+        });
+        if (rq_mem == 0) {
+          static_for<NPL>([&](auto J) { f1[J] = ba_clamp(f1[J]); });
+          asm volatile("");
+        }
+        static_for<NPL>([&](auto J) {
+          constexpr int j = J;
+          const uint32_t key = sel_mask(fm[j], wmad_s(wf9, (uint32_t)score_la_cpu(c_la[j], p.nz100_mem, nr[j]),
+                                                      wmad_s(wb9, (uint32_t)score_ba_fractions(c_f0[j], f1[j], nr[j]), kc[j])));
           b2 = max(b2, min(b1, key));
           b1 = max(b1, key);
-          feas += (uint32_t)__popcll(fm);
+          feas += (uint32_t)__popcll(fm[j]);
         });
       } else {
         static_for<NPL>([&](auto J) {
@@ -370,7 +403,7 @@ void sweep_kernel(RoundArgs a) {
       }
       const bool conflict = p.flags & PF_NA_CONFLICT;
       if (p.flags & PF_NA) preferred_raw_n<NPL, LWU>(p, a.clauses, ne, nr, praw);
-      const double *ip = fix ? a.norm_inv + 2 * r : a.guess_inv + 2 * (size_t)pi;  // RN(1 / max)
+      const double *ip = fix ? a.norm_inv + 2 * r : a.guess_inv + 2 * (size_t)(start + r);  // RN(1 / max)
       const double inv_tt = (p.flags & PF_TT) ? ip[0] : 0.0;
       const double inv_na = (p.flags & PF_NA) ? ip[1] : 0.0;
       // request > Allocatable - Requested as Requested + request > Allocatable
@@ -498,13 +531,80 @@ void sweep_kernel(RoundArgs a) {
   // resource-only kernels take the pods in batches of WL_T: they set the
   // lanes' two best keys aside per pod and reduce a batch's lists together.
   if constexpr (EXT) {
-    for (uint32_t it = p0; it < p1; ++it) sweep_pod(it, 0u);
+    for (uint32_t it = p0; it < p1; ++it) {
+      // FIX mode: slice entry it - start of the compacted flagged-pod list
+      const uint32_t r = fix ? uniform_u32(a.fix_list[it - start]) : dedup ? uniform_u32(a.ulist[it - start]) : it - start;
+      if (fix && r == FIX_NONE) continue;
+      const PodDev p = a.pods[start + r];
+      sweep_pod(it, 0u, r, p);
+    }
   } else {
+    // A pod's list entry and its descriptor are two dependent memory round
+    // trips in front of ~500 issue cycles of arithmetic, and the SIMD's other
+    // waves run the same loop: both are fetched ahead.
+    // * Lane l < p1 - p0 loads the list entry of the group's pod l: one
+    //   vector load per workgroup, in flight with the node loads above (a
+    //   group has at most MAX_PG = 64 pods; without a list the entry is the
+    //   window index).  A pod takes its entry by v_readlane.  The other lanes
+    //   load nothing: from p1 <= start + *nuniq on the list buffer holds no
+    //   entries, and what it holds never becomes an address.
+    // * The scalar load of pod q + 1's descriptor is issued before pod q's
+    //   arithmetic and first used after it.  The descriptors alternate between
+    //   two register sets (pa: even q, pb: odd q), so none is copied.  The
+    //   group's last pod has no successor and loads none: the pods array may
+    //   end with it.
+    // * A batch's last pod requests the next batch's first descriptor like any
+    //   other, in front of its own arithmetic: the batch step below starts no
+    //   round trip.  (A batch with a successor is full and WL_T is even: the
+    //   next batch starts on pa again.)
+    static_assert(MAX_PG <= WAVE && WL_T % 2 == 0, "one list entry per lane; batches start on pa");
     const uint32_t bq = lane % WL_T, bg = lane / WL_T;  // the batch step's pod and lane segment of this lane
+    uint32_t ev = p0 - start + lane;
+    if (dedup && lane < p1 - p0) ev = a.ulist[ev];
+    auto load_ahead = [&](const uint32_t it, PodDev &p) __attribute__((always_inline)) {
+      if (it < p1) p = load_pod_requests(a.pods, start + (uint32_t)__builtin_amdgcn_readlane((int)ev, (int)(it - p0)));
+    };
+    // The wait for a descriptor belongs behind the arithmetic it was issued in
+    // front of.  Scalar loads return out of order, so a wait for one is a wait
+    // for all: left at the descriptor's first use, behind the next load's
+    // issue, it would wait for that one too.  arrived() is that wait and a use
+    // the compiler sees; in_use() is a use in front of the next load's issue,
+    // where the compiler puts a wait of its own at the loop's head (an idle
+    // one: nothing is in flight there).
+    auto in_use = [&](const PodDev &p) __attribute__((always_inline)) { asm volatile("" ::"s"(f64_bits(p.req_cpu_d))); };
+    auto arrived = [&](const PodDev &p) __attribute__((always_inline)) {
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+      in_use(p);
+    };
+    PodDev pa = {}, pb = {};
+    load_ahead(p0, pa);
     for (uint32_t b0 = p0; b0 < p1; b0 += WL_T) {
-      const uint32_t nb = min((uint32_t)WL_T, p1 - b0);
+      const uint32_t nb = smin_u32((uint32_t)WL_T, p1 - b0);  // wave-uniform, kept scalar
+      if constexpr (GF == 0) {
 #pragma nounroll
-      for (uint32_t q = 0; q < nb; ++q) sweep_pod(b0 + q, q);
+        for (uint32_t q = 0;;) {
+          in_use(pa);
+          load_ahead(b0 + q + 1, pb);
+          sweep_pod(b0 + q, q, 0u, pa);
+          arrived(pb);
+          if (++q >= nb) break;
+          load_ahead(b0 + q + 1, pa);
+          sweep_pod(b0 + q, q, 0u, pb);
+          arrived(pa);
+          if (++q >= nb) break;
+        }
+      } else {
+        // the strategy scorers' bodies are large and their widest instance has
+        // no register to spare for a second copy: one body, the descriptor
+        // moved between the sets (four scalar moves per pod)
+#pragma nounroll
+        for (uint32_t q = 0; q < nb; ++q) {
+          pb = pa;
+          load_ahead(b0 + q + 1, pa);
+          sweep_pod(b0 + q, q, 0u, pb);
+          arrived(pa);
+        }
+      }
       // Batch step: lane L takes pod L % WL_T and the pairs of lanes
       // [WL_SEG (L / WL_T), + WL_SEG), folds them with per-lane min / max, and
       // the WL_T segments of a pod (lanes WL_T apart) meet in three exchanges.
@@ -928,7 +1028,7 @@ __global__ __launch_bounds__(PATCH_THREADS) void patch_kernel(RoundArgs a) {
   if (a.rep != nullptr && uniform_u32(a.rep[r]) != r) return;
   const uint32_t nc = uniform_u32(*a.carry_in_n);
   if (nc == 0) return;
-  const PodDev p = load_pod(a.pods, start + r);
+  const PodDev p = a.pods[start + r];
   uint64_t *rec = a.frec + (size_t)r * rec_words(a.K);
   ShardRecHdr *hdr = (ShardRecHdr *)rec;
   const uint64_t bound = hdr->bound;

@@ -77,6 +77,20 @@ __device__ __forceinline__ uint32_t smax_u32(uint32_t a, uint32_t b) {
   return r;
 }
 
+__device__ __forceinline__ uint32_t smin_u32(uint32_t a, uint32_t b) {
+  uint32_t r;
+  asm("s_min_u32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
+  return r;
+}
+// The lane mask of the wave-uniform condition x == 0: all lanes or none, by a
+// scalar compare and select (a ballot of it is a 64-bit VALU compare on SGPR
+// operands; a plain select moved the masks it meets into VGPRs).
+__device__ __forceinline__ uint64_t uniform_zero_mask(uint64_t x) {
+  uint64_t r;
+  asm("s_cmp_eq_u64 %1, 0\n\ts_cselect_b64 %0, -1, 0" : "=s"(r) : "s"(x) : "scc");
+  return r;
+}
+
 // DPP lane moves (no LDS): quad_perm(1,0,3,2) = 0xB1, quad_perm(2,3,0,1) = 0x4E,
 // row_half_mirror = 0x141, row_mirror = 0x140.
 template <int CTRL>

@@ -18,7 +18,10 @@ for ITS instruction mix, not a constant per instruction.  This tool:
      resource-only kernels recompute a node's cpu terms only where the pod's
      cpu key changes: their pod loop is priced as the hit path (pod_valu) +
      miss_rate x the cpu block (cpu_block_valu), with the miss rate a
-     parameter (--miss-rate, default MISS_RATE) recorded in the JSON;
+     parameter (--miss-rate, default MISS_RATE) recorded in the JSON.  Their
+     pod loop holds the pod's body once per descriptor register set (two,
+     taken in turn): counts are per pod, a turn's divided by pods_per_turn,
+     and the clamp that only zero requests run is left out;
   3. prices each opcode with the issue cost measured on MI355X at 4 waves per
      SIMD by tools/valu_issue.hip (profiles/valu_issue.jsonl); an opcode the
      microbenchmark does not cover takes its class's median (VOP1/VOP2
@@ -159,25 +162,42 @@ def cpu_block(ins, outer, inner):
     """The pod loop's conditional block: the resource-only kernels
     of the default strategy keep each node's cpu terms while the pod's cpu key
     (req_cpu, nz_cpu) stays, and recompute them behind a wave-uniform branch on
-    a compare of two SGPR pairs.  One turn of the loop is walked from that
-    branch in both directions (other conditional branches fall through: they
-    leave the loop or skip a load; s_cbranch_exec* never jump, the wave is
-    whole), and the turn with fewer VALU instructions is the hit path.
-    Returns (hit addresses, miss-only addresses), or None without such a
-    branch (every other kernel)."""
+    a compare of two SGPR pairs.  The loop holds one copy of the pod's body per
+    descriptor register set (two, taken in turn), so a turn of the
+    loop is that many pods and that many such branches.  One turn is walked
+    from the first of them with all of them taken, and one with none taken;
+    the turn with fewer VALU instructions is the hit path.  The loop's own
+    backward branch is taken.  A conditional branch over nothing but the
+    clamp of the BalancedAllocation fractions (v_max_f64 / v_min_f64 and
+    scalar instructions) is taken too: the clamp runs for zero requests only
+    and is not priced.  Other conditional branches fall through: they leave
+    the loop or skip a load; s_cbranch_exec* never jump, the wave is whole.
+    Returns (hit addresses, miss-only addresses, pods per turn), or None
+    without such a branch (every other kernel)."""
     body = [(a, op, args) for a, op, args in ins if inner[0] <= a < inner[1]]
     # (a turn may re-enter a few scalar moves above the longest branch's target)
     lo = min([inner[0]] + [branch_target(a, args) for a, op, args in body
                            if op == "s_branch" and outer[0] <= branch_target(a, args)])
     body = [(a, op, args) for a, op, args in ins if lo <= a < inner[1]]
     at = {a: i for i, (a, _, _) in enumerate(body)}
-    key = None
+    keys = []
     for i, (a, op, args) in enumerate(body):
-        if KEY_CMP.match(op) and SGPR_PAIRS.match(args):
-            key = next((j for j in range(i + 1, len(body)) if body[j][1] in COND), None)
-            break
-    if key is None:
+        if KEY_CMP.match(op) and SGPR_PAIRS.match(args) and (not keys or i > keys[-1]):
+            k = next((j for j in range(i + 1, len(body)) if body[j][1] in COND), None)
+            if k is not None:
+                keys.append(k)
+    if not keys:
         return None
+    key = keys[0]
+
+    def over_clamp_only(i):
+        a, op, args = body[i]
+        j = at.get(branch_target(a, args)) if op in COND else None
+        if j is None or j <= i + 1:
+            return False
+        ops = [body[k][1] for k in range(i + 1, j)]
+        return any(o.startswith("v_min_f64") for o in ops) and all(
+            o.startswith(("v_max_f64", "v_min_f64", "s_")) and not o.startswith(("s_cbranch", "s_branch")) for o in ops)
 
     def turn(taken):
         seen, i = [], key
@@ -186,7 +206,8 @@ def cpu_block(ins, outer, inner):
             if i == key and seen:
                 return seen
             seen.append(a)
-            jump = op == "s_branch" or (i == key and taken)
+            jump = (op == "s_branch" or (i in keys and taken) or (i == len(body) - 1 and op in COND) or
+                    over_clamp_only(i))
             nxt = at.get(branch_target(a, args)) if jump else i + 1
             if nxt is None or nxt >= len(body) or len(seen) > len(body):
                 raise RuntimeError("the pod loop's turn leaves the loop")
@@ -195,7 +216,7 @@ def cpu_block(ins, outer, inner):
     valu = lambda path: sum(1 for a in path if body[at[a]][1].startswith("v_"))
     p, q = turn(True), turn(False)
     hit, miss = (p, q) if valu(p) <= valu(q) else (q, p)
-    return set(hit), set(miss) - set(hit)
+    return set(hit), set(miss) - set(hit), len(keys)
 
 
 def general_variant(mangled: str) -> bool:
@@ -251,13 +272,22 @@ def main():
             raise RuntimeError(f"{targs}: no pod loop inside the loop over the batches")
         blk = cpu_block(ins, (lo, hi), inner) if batched else None
         miss_only = blk[1] if blk else set()
+        turn_pods = blk[2] if blk else 1  # copies of the pod's body in the pod loop
+        on_path = (blk[0] | blk[1]) if blk else None
         # (opcode, operands, weight): the batch step's instructions run once per
-        # T pods, the cpu block's once per miss_rate pods
-        loop = [(op, args, miss_rate if a in miss_only else 1.0 if not batched or inner[0] <= a < inner[1] else 1.0 / T)
-                for a, op, args in ins if lo <= a < hi and op.startswith("v_")]
+        # T pods, the cpu block's once per miss_rate pods; a turn of the pod
+        # loop is turn_pods pods, and what no turn reaches (the clamp) has no weight
+        def weight(a):
+            if not batched or not (inner[0] <= a < inner[1]):
+                return 1.0 / T if batched else 1.0
+            if on_path is not None and a not in on_path:
+                return 0.0
+            return (miss_rate if a in miss_only else 1.0) / turn_pods
+        loop = [(op, args, weight(a)) for a, op, args in ins if lo <= a < hi and op.startswith("v_") and weight(a) > 0]
         in_batch = lambda a: batched and not (inner[0] <= a < inner[1])
         hist = collections.Counter(op for a, op, _ in ins
-                                   if lo <= a < hi and op.startswith("v_") and not in_batch(a) and a not in miss_only)
+                                   if lo <= a < hi and op.startswith("v_") and not in_batch(a) and a not in miss_only and
+                                   (on_path is None or a in on_path))
         mhist = collections.Counter(op for a, op, _ in ins if a in miss_only and op.startswith("v_"))
         bhist = collections.Counter(op for a, op, _ in ins if lo <= a < hi and op.startswith("v_") and in_batch(a))
         n = sum(w for _, _, w in loop)
@@ -270,19 +300,20 @@ def main():
              "measured_share": round(covered / n, 4),
              "hist": dict(hist.most_common())}
         if batched:
-            k.update(pod_valu=sum(hist.values()), batch_valu=sum(bhist.values()), batch_pods=T,
-                     batch_hist=dict(bhist.most_common()))
+            k.update(pod_valu=sum(hist.values()) / turn_pods, batch_valu=sum(bhist.values()), batch_pods=T,
+                     batch_hist=dict(bhist.most_common()), pods_per_turn=turn_pods)
         if blk:
             # pod_valu: the hit path; a pod whose cpu key differs from its
             # predecessor's adds cpu_block_valu
-            k.update(cpu_block_valu=sum(mhist.values()), miss_rate=miss_rate, cpu_block_hist=dict(mhist.most_common()))
+            k.update(cpu_block_valu=sum(mhist.values()) / turn_pods, miss_rate=miss_rate,
+                     cpu_block_hist=dict(mhist.most_common()))
         res["kernels"][targs] = k
     out = ROOT / "profiles" / "valu_mix.json"
     out.write_text(json.dumps(res, indent=1) + "\n")
     for k, v in sorted(res["kernels"].items()):
-        parts = f" = {v['pod_valu']} + {v['batch_valu']} / {v['batch_pods']}" if "pod_valu" in v else ""
+        parts = f" = {v['pod_valu']:g} + {v['batch_valu']} / {v['batch_pods']}" if "pod_valu" in v else ""
         if "cpu_block_valu" in v:
-            parts += f" + {v['miss_rate']} x {v['cpu_block_valu']}"
+            parts += f" + {v['miss_rate']} x {v['cpu_block_valu']:g}"
         print(f"sweep_kernel{k}: {v['loop_valu']}{parts} VALU per pod in the pod loop, {v['cycles_per_valu']} cycles each "
               f"(measured opcodes {v['measured_share']:.0%})")
     print("->", out.relative_to(ROOT))
