@@ -1076,6 +1076,105 @@ typedef struct {
  * ks_schedule then chooses within its window, which need not hold out[0]. */
 ks_status ks_explain(ks_ctx *ctx, const ks_pod *pod, uint32_t k, ks_explanation *e, ks_candidate *out);
 
+/* ------------------------------------------------- capacity */
+/* How many more replicas of a pod the cluster holds, and what runs out first:
+ * the answer upstream's cluster-capacity tool finds by scheduling replica
+ * after replica on a copy of the cluster until the first FitError.  For the
+ * pods these calls accept, replicas stop fitting on a node only through
+ * NodeResourcesFit (and NodePorts, where the pod conflicts with itself); every
+ * other filter's verdict on a node does not change as replicas land, and
+ * scores decide the order of placement, never whether one more fits.  So a
+ * node that passes every filter before NodeResourcesFit ends up holding
+ *
+ *   c = min(free pod slots, floor(free_r / req_r) for every resource r with req_r > 0)
+ *
+ * more replicas, capped at 1 where the pod has host ports, and the cluster
+ * holds the sum, whatever the scoring profile, the fit strategy, the tie-break
+ * and percentage_of_nodes_to_score.  One node-parallel pass computes it from
+ * the resident columns and commits nothing.
+ *
+ *   free pod slots  max(0, allocatable pods - pods on the node)
+ *   free_r          max(0, Allocatable_r - Requested_r), on the columns
+ *                   fitsRequest reads (Requested, not NonZeroRequested)
+ *   req_r           the pod's request as ks_diagnose tests it: overhead, init
+ *                   containers and sidecars included; ephemeral-storage and
+ *                   scalar resources through the pod's extended requests
+ * A resource the pod requests 0 of does not bind; a pod that requests nothing
+ * is bound by pod slots alone (fitsRequest returns early).  Where the pod has
+ * host ports a node whose used ports conflict with them now is not eligible
+ * (NodePorts comes before NodeResourcesFit); on every other eligible node
+ * c = min(c, 1).  The quotients are exact for every int64 the columns hold.
+ *
+ * bound_by counts every eligible node, c == 0 included, under the first term
+ * that attains its minimum, in the order KS_CAP_PODS, KS_CAP_CPU,
+ * KS_CAP_MEMORY, the pod's extended-resource columns ascending (KS_CAP_X + k
+ * for column k, the order ks_diagnose names them in), KS_CAP_PORTS last: ports
+ * bind only where everything else allows two or more.  The bins sum to
+ * eligible_nodes. */
+enum { KS_CAP_PODS = 0, KS_CAP_CPU = 1, KS_CAP_MEMORY = 2, KS_CAP_PORTS = 3, KS_CAP_X = 4, KS_CAP_BOUNDS = 12 };
+typedef struct {
+  uint32_t num_all_nodes;    /* present nodes */
+  uint32_t eligible_nodes;   /* pass every filter before NodeResourcesFit (NodePorts against
+                                the node's present used ports included) */
+  uint32_t nodes_with_room;  /* c >= 1: equals ks_diagnose's feasible_nodes */
+  uint32_t max_per_node;     /* max c */
+  uint64_t replicas;         /* sum of c */
+  uint32_t bound_by[KS_CAP_BOUNDS];  /* eligible nodes per binding term */
+  const char *x_names[8];    /* x_names[k]: the resource of column k where the pod requests it (owned
+                                by the context until the next ks_capacity_pod / ks_capacity_pods or
+                                ks_close), else NULL */
+} ks_capacity;
+
+/* One pod against the cache as it is.  per_node is NULL or has room for
+ * node_capacity entries: per_node[slot] is the slot's c, 0 for an absent or
+ * ineligible slot.  With NULL a few hundred bytes come back, whatever the
+ * node count.
+ *
+ * The call shares ks_diagnose's rules: it waits for submitted batches, commits
+ * nothing and interns nothing (no host-port triple, no selector class that
+ * outlives the call, no resource name), leaves nextStartNodeIndex alone, is
+ * over every present node whatever percentage_of_nodes_to_score, and on a
+ * multi-rank context answers from the rank's own replica of the node table.
+ *
+ * Refused, never approximated: a pod ks_pods_check refuses, with the same
+ * status and error text; and with KS_ERR_UNSUPPORTED, the reason named in
+ * ks_last_error, a pod with a DoNotSchedule topology spread constraint, a pod
+ * with required pod affinity or anti-affinity terms, and a pod that a bound
+ * pod's required anti-affinity term selects -- their count depends on where
+ * the replicas land.  ScheduleAnyway constraints, preferred pod (anti-)affinity
+ * and images only score: accepted and ignored.  A null ctx, pod or out is
+ * KS_ERR_INVALID. */
+ks_status ks_capacity_pod(ks_ctx *ctx, const ks_pod *pod, ks_capacity *out, uint32_t *per_node);
+
+/* ks_capacity_pod for a list of pods in one call, with ks_diagnose_pods'
+ * conventions: one compile, one upload, one pass over the node rows for every
+ * group of pods without a one-pod program (the others take the per-pod pass,
+ * launched back to back), one read-back and one wait; byte-identical compiled
+ * pods are answered once.  Each pod is answered on its own against the one
+ * cache state the call finds: out[i].c is what ks_capacity_pod returns for
+ * pods[i] alone.  The joint capacity of a mix of shapes depends on the order
+ * they are placed in and is not what this call answers.
+ *
+ * A refused pod gets its status in out[i].status and a zeroed record; the
+ * other pods are still answered, the call returns the first refused pod's
+ * status and ks_last_error names its index.  A device error ends the call.
+ * n == 0 is KS_OK; a null ctx, or null pods or out with n > 0, is
+ * KS_ERR_INVALID. */
+typedef struct {
+  ks_status status;  /* KS_OK, or the status ks_capacity_pod returns for this pod */
+  uint32_t _pad;
+  ks_capacity c;     /* exactly as ks_capacity_pod fills it (zeroed when status != KS_OK) */
+} ks_pod_capacity;
+ks_status ks_capacity_pods(ks_ctx *ctx, const ks_pod *pods, uint32_t n, ks_pod_capacity *out);
+/* The most recent ks_capacity_pod / ks_capacity_pods call (tests prove by it
+ * which path ran): [0] distinct pods the multi-pod kernel answered, [1]
+ * distinct pods answered by the per-pod pass, [2] identical pods not answered
+ * again, [3] launches of the multi-pod kernel, [4] its pods per group, [5]
+ * node positions one launch covers before its grid-stride loop takes a second
+ * turn ([4] and [5] are constants of the build, set before any call), [6] and
+ * [7] 0. */
+ks_status ks_debug_capacity(ks_ctx *ctx, uint64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@
 
 #include "ksched.h"
 #include "ksched_ba.hpp"
+#include "ksched_capacity.hpp"
 #include "ksched_dev.hpp"
 #include "ksched_diag.hpp"
 #include "ksched_explain.hpp"
@@ -630,6 +631,11 @@ struct ks_ctx {
   std::vector<std::string> dp_strs;
   std::string dp_prefilter;
   uint64_t dp_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // ks_capacity_pod / ks_capacity_pods: the extended-resource
+  // names the last call handed out (one per column), and its counters
+  // (ks_debug_capacity)
+  std::string cap_names[MAX_XRES];
+  uint64_t cap_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // ks_explain: the blocks' key lists and tie pairs, the
   // final keys and the record, allocated by the first call
   struct ExplainDev {
@@ -5277,6 +5283,121 @@ ks_status diagnose_pods_rerun(ks_ctx *c, const PodDev &d, const std::vector<uint
   return KS_OK;
 }
 
+// The front ks_diagnose_pods and ks_capacity_pods share: ks_pods_check's
+// verdict on each pod, the accepted pods compiled as a batch compiles them (no
+// host-port triple interned), the context's device columns brought up to
+// date, and the distinct compiled pods in launch order.
+constexpr uint32_t POD_REFUSED = 0xFFFFFFFFu;
+struct PodsFront {
+  uint32_t first_idx = POD_REFUSED;  // the first refused pod, its status and text
+  ks_status first = KS_OK;
+  std::string first_err;
+  std::vector<ks_pod> acc;       // the accepted pods
+  std::vector<uint32_t> acc_of;  // ... their indices in pods
+  std::vector<PodDev> dev;
+  std::vector<uint32_t> tag;     // per accepted pod: what the call tells apart beyond the compiled pod
+  ProgBuf cl;
+  uint64_t epoch0 = 0;
+  uint32_t num_all = 0;
+  std::vector<uint32_t> rep;     // accepted pod -> the first of its class (POD_REFUSED: refused after the compile)
+  std::vector<uint32_t> order;   // the distinct pods: plain without PF_EXT, plain with, one-pod chain
+  std::vector<uint32_t> at;      // distinct pod -> its index in order
+  uint32_t n_plain = 0, n_ext = 0, n_solo = 0;
+
+  void refuse(uint32_t i, ks_status st, const std::string &why) {
+    if (i >= first_idx) return;
+    first_idx = i;
+    first = st;
+    first_err = "pod " + std::to_string(i) + ": " + why;
+  }
+};
+
+// verdict(i, status): pod i's entry of the call's output (zeroed, with the
+// status); locked(): the call's own allocations and reads under the context's
+// lock, after the compile and the uploads.
+ks_status pods_front_compile(ks_ctx *c, const ks_pod *pods, uint32_t n, const std::function<void(uint32_t, ks_status)> &verdict,
+                             const std::function<ks_status()> &locked, PodsFront *f) {
+  ks_status st = KS_OK;
+  std::unique_lock<std::mutex> g(c->mu);
+  for (uint32_t i = 0; i < n; ++i) {  // ks_pods_check's verdict on each pod, with its status and text
+    PodDev d0;
+    ProgBuf cl0;
+    const ks_status s = compile_batch(c, &pods[i], 1, &d0, cl0, g);
+    verdict(i, s);
+    if (s) {
+      std::lock_guard<std::mutex> ge(c->err_mu);
+      f->refuse(i, s, c->err);
+      continue;
+    }
+    f->acc.push_back(pods[i]);
+    f->acc_of.push_back(i);
+  }
+  f->epoch0 = c->class_epoch;
+  f->dev.resize(std::max<size_t>(f->acc.size(), 1));
+  f->tag.assign(f->acc.size(), 0);
+  if (!f->acc.empty()) {
+    c->compile_for_dump = true;  // no host-port triple interned
+    st = compile_batch(c, f->acc.data(), (uint32_t)f->acc.size(), f->dev.data(), f->cl, g, true);
+    c->compile_for_dump = false;
+    if (!st) st = upload_dirty_ext(c, c->xm);
+    if (!st) st = spread_alloc(c);  // the position -> slot column
+    if (!st) st = locked();
+  }
+  f->num_all = c->n_present;
+  return st;
+}
+
+// selector classes the compile created are dropped again, whatever happened in between
+void pods_front_drop(ks_ctx *c, const PodsFront &f) {
+  std::lock_guard<std::mutex> g(c->mu);
+  for (int k = 0; k < MAX_CLASSES; ++k) {
+    SpreadClass &sc = c->classes[k];
+    if (!sc.live || sc.born <= f.epoch0 || sc.refs) continue;
+    c->class_of.erase(sc.canon);
+    sc = SpreadClass();
+  }
+}
+
+// identical compiled pods (descriptor, program words and tag) are answered once: rep[j] the first of j's class
+void pods_front_classes(PodsFront *f) {
+  const uint32_t m = (uint32_t)f->acc.size();
+  const std::vector<PodDev> &dev = f->dev;
+  f->rep.resize(m);
+  std::unordered_map<uint64_t, uint32_t> seen;
+  seen.reserve(m);
+  for (uint32_t j = 0; j < m; ++j) {
+    if (f->rep[j] == POD_REFUSED) continue;
+    PodDev x = dev[j];
+    x.req_off = x.pref_off = x.solo_off = x.pre_off = 0;
+    uint64_t h = 1469598103934665603ull;  // FNV-1a over the descriptor's words (pod_classes)
+    const uint64_t *w = reinterpret_cast<const uint64_t *>(&x);
+    for (size_t q = 0; q < sizeof(PodDev) / 8; ++q) h = (h ^ w[q]) * 1099511628211ull;
+    h = (h ^ f->tag[j]) * 1099511628211ull;
+    f->rep[j] = j;
+    for (;; ++h) {
+      auto it = seen.find(h);
+      if (it == seen.end()) {
+        seen.emplace(h, j);
+        break;
+      }
+      if (f->tag[it->second] == f->tag[j] && same_pod_program(dev[it->second], dev[j], f->cl.w.data())) {
+        f->rep[j] = it->second;
+        break;
+      }
+    }
+  }
+  for (int kind = 0; kind < 3; ++kind)
+    for (uint32_t j = 0; j < m; ++j) {
+      if (f->rep[j] != j) continue;
+      const int k = (dev[j].flags & PF_SOLO) ? 2 : (dev[j].flags & PF_EXT) ? 1 : 0;
+      if (k != kind) continue;
+      f->order.push_back(j);
+      ++(k == 0 ? f->n_plain : k == 1 ? f->n_ext : f->n_solo);
+    }
+  f->at.assign(m, 0);
+  for (uint32_t k = 0; k < (uint32_t)f->order.size(); ++k) f->at[f->order[k]] = k;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5295,98 +5416,41 @@ ks_status ks_diagnose_pods(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_pod_dia
   std::memcpy(c->dp_ctr, ctr, sizeof ctr);
   if (!n) return KS_OK;
   HIPC(c, hipSetDevice(c->cfg.device));
-  ks_status st = KS_OK, first = KS_OK;
-  std::string first_err;
-  std::vector<ks_pod> acc;       // the accepted pods
-  std::vector<uint32_t> acc_of;  // ... their indices in pods
-  std::vector<PodDev> dev;
-  ProgBuf cl;
-  uint64_t epoch0;
-  uint32_t num_all;
   DiagNames nm;
+  PodsFront f;
+  ks_status st = pods_front_compile(
+      c, pods, n,
+      [&](uint32_t i, ks_status s) {
+        std::memset(&out[i], 0, sizeof out[i]);
+        out[i].status = s;
+      },
+      [&]() -> ks_status {
+        ks_status s = KS_OK;
+        if (!c->d_diag_rec && !(s = dalloc(c, &c->d_diag_rec, 1))) s = dalloc(c, &c->d_diag_list, c->cap);
+        if (!s && !c->d_dp_list && !(s = dalloc(c, &c->d_dp_list, DP_LIST_PER_NODE * c->cap)) &&
+            !(s = dalloc(c, &c->d_dp_list_n, 1)))
+          s = dalloc(c, &c->d_dp_solo_list, DP_LIST_PER_NODE * c->cap);
+        return s;
+      },
+      &f);
   {
-    std::unique_lock<std::mutex> g(c->mu);
-    for (uint32_t i = 0; i < n; ++i) {  // ks_pods_check's verdict on each pod, with its status and text
-      PodDev d0;
-      ProgBuf cl0;
-      std::memset(&out[i], 0, sizeof out[i]);
-      if ((out[i].status = compile_batch(c, &pods[i], 1, &d0, cl0, g))) {
-        if (!first) {
-          first = out[i].status;
-          std::lock_guard<std::mutex> ge(c->err_mu);
-          first_err = "pod " + std::to_string(i) + ": " + c->err;
-        }
-        continue;
-      }
-      acc.push_back(pods[i]);
-      acc_of.push_back(i);
-    }
-    epoch0 = c->class_epoch;
-    dev.resize(std::max<size_t>(acc.size(), 1));
-    if (!acc.empty()) {
-      c->compile_for_dump = true;  // no host-port triple interned
-      st = compile_batch(c, acc.data(), (uint32_t)acc.size(), dev.data(), cl, g, true);
-      c->compile_for_dump = false;
-      if (!st) st = upload_dirty_ext(c, c->xm);
-      if (!st) st = spread_alloc(c);  // the position -> slot column
-      if (!st && !c->d_diag_rec && !(st = dalloc(c, &c->d_diag_rec, 1))) st = dalloc(c, &c->d_diag_list, c->cap);
-      if (!st && !c->d_dp_list && !(st = dalloc(c, &c->d_dp_list, DP_LIST_PER_NODE * c->cap)) &&
-          !(st = dalloc(c, &c->d_dp_list_n, 1)))
-        st = dalloc(c, &c->d_dp_solo_list, DP_LIST_PER_NODE * c->cap);
-    }
-    num_all = c->n_present;
+    std::lock_guard<std::mutex> g(c->mu);
     for (size_t b = 0; b < c->hard_list.size() && b < (size_t)DIAG_TAINT_BINS; ++b)
       nm.taint[b] = diag_taint_reason(c->strs[c->hard_list[b].key], c->strs[c->hard_list[b].value]);
     for (size_t x = 0; x < c->xres_names.size() && x < 8; ++x) nm.xres[x] = c->strs[c->xres_names[x]];
   }
-  // selector classes the compile created are dropped again below, whatever happens in between
-  auto drop_classes = [&] {
-    std::lock_guard<std::mutex> g(c->mu);
-    for (int k = 0; k < MAX_CLASSES; ++k) {
-      SpreadClass &sc = c->classes[k];
-      if (!sc.live || sc.born <= epoch0 || sc.refs) continue;
-      c->class_of.erase(sc.canon);
-      sc = SpreadClass();
-    }
-  };
-  const uint32_t m = (uint32_t)acc.size();
-  // identical compiled pods (descriptor and program words) are diagnosed once: rep[j] the first of j's class
-  std::vector<uint32_t> rep(m), order;  // order: the distinct pods -- plain without PF_EXT, plain with, one-pod chain
-  uint32_t n_plain = 0, n_ext = 0, n_solo = 0;
-  if (!st && m) {
-    std::unordered_map<uint64_t, uint32_t> seen;
-    seen.reserve(m);
-    for (uint32_t j = 0; j < m; ++j) {
-      PodDev x = dev[j];
-      x.req_off = x.pref_off = x.solo_off = x.pre_off = 0;
-      uint64_t h = 1469598103934665603ull;  // FNV-1a over the descriptor's words (pod_classes)
-      const uint64_t *w = reinterpret_cast<const uint64_t *>(&x);
-      for (size_t q = 0; q < sizeof(PodDev) / 8; ++q) h = (h ^ w[q]) * 1099511628211ull;
-      rep[j] = j;
-      for (;; ++h) {
-        auto it = seen.find(h);
-        if (it == seen.end()) {
-          seen.emplace(h, j);
-          break;
-        }
-        if (same_pod_program(dev[it->second], dev[j], cl.w.data())) {
-          rep[j] = it->second;
-          break;
-        }
-      }
-    }
-    for (int kind = 0; kind < 3; ++kind)
-      for (uint32_t j = 0; j < m; ++j) {
-        if (rep[j] != j) continue;
-        const int k = (dev[j].flags & PF_SOLO) ? 2 : (dev[j].flags & PF_EXT) ? 1 : 0;
-        if (k != kind) continue;
-        order.push_back(j);
-        ++(k == 0 ? n_plain : k == 1 ? n_ext : n_solo);
-      }
-  }
+  auto drop_classes = [&] { pods_front_drop(c, f); };
+  const ks_status first = f.first;
+  const std::string &first_err = f.first_err;
+  const std::vector<uint32_t> &acc_of = f.acc_of;
+  const std::vector<PodDev> &dev = f.dev;
+  ProgBuf &cl = f.cl;
+  const uint32_t num_all = f.num_all;
+  const uint32_t m = (uint32_t)f.acc.size();
+  if (!st && m) pods_front_classes(&f);
+  const std::vector<uint32_t> &rep = f.rep, &order = f.order, &at = f.at;
+  const uint32_t n_plain = f.n_plain, n_ext = f.n_ext, n_solo = f.n_solo;
   const uint32_t D = (uint32_t)order.size();
-  std::vector<uint32_t> at(m, 0);  // distinct pod -> its index in order
-  for (uint32_t k = 0; k < D; ++k) at[order[k]] = k;
   // an empty one-pod program, for a plain pod that has to take ks_diagnose's pass after all
   if (cl.w.size() & 1) cl.w.push_back(0);
   const uint32_t empty_solo = (uint32_t)cl.w.size();
@@ -5544,6 +5608,193 @@ ks_status ks_debug_diagnose_pods(ks_ctx *c, uint64_t out[8]) {
   std::memcpy(out, c->dp_ctr, sizeof c->dp_ctr);
   out[5] = DPB_GROUP;
   out[6] = (uint64_t)DPB_MAX_BLOCKS * DPB_THREADS;
+  return KS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Why ks_capacity refuses a compiled pod, read off the
+// records of its one-pod program -- what makes the chain run a prep / min pass
+// or an InterPodAffinity filter for it; null: accepted.
+const char *capacity_refusal(const PodDev &d, const uint64_t *w) {
+  if (!(d.flags & PF_SOLO)) return nullptr;
+  const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(w + d.solo_off);
+  const SpreadDev *sd = reinterpret_cast<const SpreadDev *>(hd + 1);
+  for (uint32_t k = 0; k < hd->n_spread; ++k)
+    if (!(sd[k].flags & SP_SCORE)) return "a DoNotSchedule topology spread constraint";
+  const AffDev *ad = reinterpret_cast<const AffDev *>(reinterpret_cast<const ImageDev *>(
+                                                          reinterpret_cast<const XResDev *>(sd + hd->n_spread) + hd->n_xres) +
+                                                      hd->n_img);
+  for (uint32_t k = 0; k < hd->n_aff; ++k) {
+    const uint32_t kind = ad[k].kind & AF_KIND;
+    if (kind == AF_REQ_AFF) return "a required pod affinity term";
+    if (kind == AF_REQ_ANTI) return "a required pod anti-affinity term";
+    if (kind == AF_EXIST_ANTI) return "a bound pod's required anti-affinity term selects it";
+  }
+  return nullptr;
+}
+
+// ks_capacity_pod / ks_capacity_pods: ks_diagnose_pods' front, the refusals,
+// the multi-pod kernel for the pods without a one-pod program and the per-pod
+// pass for the others back to back, one read-back and one wait.  per_node:
+// null, or [capacity] with n == 1.
+ks_status capacity_run(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_pod_capacity *out, uint32_t *per_node) {
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  const uint64_t ctr[8] = {0, 0, 0, 0, (uint64_t)CPB_GROUP, (uint64_t)CPB_MAX_BLOCKS * CPB_THREADS, 0, 0};
+  std::memcpy(c->cap_ctr, ctr, sizeof ctr);
+  if (!n) return KS_OK;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  PodsFront f;
+  std::string names[MAX_XRES];
+  ks_status st = pods_front_compile(
+      c, pods, n,
+      [&](uint32_t i, ks_status s) {
+        std::memset(&out[i], 0, sizeof out[i]);
+        out[i].status = s;
+      },
+      [&]() -> ks_status {
+        for (size_t x = 0; x < c->xres_names.size() && x < (size_t)MAX_XRES; ++x) names[x] = c->strs[c->xres_names[x]];
+        return KS_OK;
+      },
+      &f);
+  const uint32_t m = (uint32_t)f.acc.size();
+  if (!st && m) {
+    // refused after the compile: what the closed form does not cover; told apart beyond the compiled pod: host
+    // ports (a triple no node holds leaves no trace in a read-only compile)
+    f.rep.assign(m, 0);
+    for (uint32_t j = 0; j < m; ++j) {
+      if (const char *why = capacity_refusal(f.dev[j], f.cl.w.data())) {
+        f.rep[j] = POD_REFUSED;
+        out[f.acc_of[j]].status = KS_ERR_UNSUPPORTED;
+        f.refuse(f.acc_of[j], KS_ERR_UNSUPPORTED,
+                 str(f.acc[j].ns) + "/" + str(f.acc[j].name) + ": ks_capacity does not cover " + why);
+        continue;
+      }
+      PortList want;
+      if (pod_lists_ports(f.acc[j]) && !pod_port_entries(c, f.acc[j], &want) && !want.empty()) f.tag[j] = 1;
+    }
+    pods_front_classes(&f);
+  }
+  const uint32_t D = (uint32_t)f.order.size(), n_plain = f.n_plain, n_ext = f.n_ext;
+  std::vector<CapRec> recs(D);
+  std::vector<uint32_t> cols(D, 0);  // extended-resource columns each distinct pod requests
+  if (!st && D) st = [&]() -> ks_status {
+    ks_status s;
+    std::vector<PodDev> hp(D);
+    std::vector<CapPod> cp(D);
+    const uint64_t *w = f.cl.w.data();
+    for (uint32_t k = 0; k < D; ++k) {
+      const PodDev &d = hp[k] = f.dev[f.order[k]];
+      CapPod &q = cp[k] = CapPod{};
+      q.rcp_cpu = d.req_cpu > 0 ? 1.0 / (double)d.req_cpu : 0.0;
+      q.rcp_mem = d.req_mem > 0 ? 1.0 / (double)d.req_mem : 0.0;
+      if (!(d.flags & PF_SOLO)) continue;
+      const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(w + d.solo_off);
+      const XResDev *xr = reinterpret_cast<const XResDev *>(reinterpret_cast<const SpreadDev *>(hd + 1) + hd->n_spread);
+      for (uint32_t x = 0; x < hd->n_xres && x < (uint32_t)MAX_XRES; ++x) {
+        if (xr[x].req <= 0) continue;
+        q.rcp_x[x] = 1.0 / (double)xr[x].req;
+        cols[k] |= 1u << (xr[x].col & (MAX_XRES - 1));
+      }
+    }
+    const size_t back = (size_t)D * sizeof(CapRec), pn = per_node ? (size_t)c->cap * 4 : 0;
+    const size_t up = (size_t)D * (sizeof(PodDev) + sizeof(CapPod)) + f.cl.w.size() * 8;
+    if ((s = xfer_begin(c, up + back + pn + 4096, up + back + pn + 4096))) return s;
+    PodDev *d_pods = dscratch<PodDev>(c, D);
+    CapPod *d_cp = dscratch<CapPod>(c, D);
+    uint64_t *d_cl = dscratch<uint64_t>(c, f.cl.w.size());
+    CapRec *d_recs = dscratch<CapRec>(c, D);
+    uint32_t *d_pn = per_node ? dscratch<uint32_t>(c, c->cap) : nullptr;
+    if (!d_pods || !d_cp || !d_cl || !d_recs || (per_node && !d_pn))
+      return c->fail(KS_ERR_INVALID, "capacity: device scratch overflow");
+    if ((s = h2d(c, d_pods, hp.data(), (size_t)D * sizeof(PodDev))) ||
+        (s = h2d(c, d_cp, cp.data(), (size_t)D * sizeof(CapPod))) || (s = h2d(c, d_cl, w, f.cl.w.size() * 8)))
+      return s;
+    HIPC(c, hipMemsetAsync(d_recs, 0, back, c->stream));
+    if (d_pn) HIPC(c, hipMemsetAsync(d_pn, 0, pn, c->stream));
+    SpreadArgs sa = spread_args(c);
+    CapPodsArgs pa{};
+    pa.t = sa.t;
+    pa.pos_slot = sa.pos_slot;
+    pa.npos = sa.npos;
+    pa.pods = d_pods;
+    pa.cpods = d_cp;
+    pa.clauses = d_cl;
+    pa.recs = d_recs;
+    pa.per_node = D == 1 ? d_pn : nullptr;
+    pa.first = 0;
+    pa.count = n_plain;
+    HIPC(c, launch_capacity_pods(pa, false, c->stream));
+    pa.first = n_plain;
+    pa.count = n_ext;
+    HIPC(c, launch_capacity_pods(pa, true, c->stream));
+    c->cap_ctr[3] = (n_plain ? 1 : 0) + (n_ext ? 1 : 0);
+    // the pods with a one-pod program: the per-pod pass for each, back to back, into its own record
+    sa.pods = d_pods;
+    sa.clauses = d_cl;
+    sa.no_commit = 1;
+    for (uint32_t k = n_plain + n_ext; k < D; ++k) {
+      const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(w + hp[k].solo_off);
+      sa.pod = k;
+      sa.ports_conflict = hd->ports;  // (the program holds the conflict mask itself: PORTS_DUMP)
+      const CapPodArgs ga{d_recs + k, d_cp, D == 1 ? d_pn : nullptr};
+      HIPC(c, launch_capacity_pod(sa, ga, f.tag[f.order[k]] != 0, c->stream));
+    }
+    if ((s = d2h(c, recs.data(), d_recs, back)) || (per_node && (s = d2h(c, per_node, d_pn, pn))) || (s = xfer_sync(c)))
+      return s;
+    return KS_OK;
+  }();
+  if (m) pods_front_drop(c, f);
+  if (st) return st;
+  c->cap_ctr[0] = n_plain + n_ext;
+  c->cap_ctr[1] = f.n_solo;
+  for (uint32_t j = 0; j < m; ++j) c->cap_ctr[2] += f.rep[j] != POD_REFUSED && f.rep[j] != j;
+  for (int x = 0; x < MAX_XRES; ++x) c->cap_names[x] = names[x];
+  for (uint32_t j = 0; j < m; ++j) {
+    if (f.rep[j] == POD_REFUSED) continue;
+    const uint32_t k = f.at[f.rep[j]];
+    const CapRec &r = recs[k];
+    ks_capacity &o = out[f.acc_of[j]].c;
+    o.num_all_nodes = f.num_all;
+    o.eligible_nodes = r.eligible;
+    o.nodes_with_room = r.room;
+    o.max_per_node = r.max_per_node;
+    o.replicas = r.replicas;
+    static_assert((int)CAP_TERMS == (int)KS_CAP_BOUNDS && (int)CAP_X == (int)KS_CAP_X && (int)CAP_PORTS == (int)KS_CAP_PORTS,
+                  "binding terms");
+    for (int b = 0; b < KS_CAP_BOUNDS; ++b) o.bound_by[b] = r.bound[b];
+    for (int x = 0; x < MAX_XRES; ++x) o.x_names[x] = (cols[k] >> x & 1u) ? c->cap_names[x].c_str() : nullptr;
+  }
+  if (f.first) return c->fail(f.first, "%s", f.first_err.c_str());
+  return KS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+ks_status ks_capacity_pod(ks_ctx *c, const ks_pod *pod, ks_capacity *out, uint32_t *per_node) {
+  if (!c || !pod || !out) return KS_ERR_INVALID;
+  ks_pod_capacity one;
+  std::memset(&one, 0, sizeof one);
+  const ks_status st = capacity_run(c, pod, 1, &one, per_node);
+  *out = one.c;
+  if (per_node && (st || one.status)) std::memset(per_node, 0, (size_t)c->cap * 4);
+  return st;
+}
+
+ks_status ks_capacity_pods(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_pod_capacity *out) {
+  if (!c || (n && (!pods || !out))) return KS_ERR_INVALID;
+  return capacity_run(c, pods, n, out, nullptr);
+}
+
+ks_status ks_debug_capacity(ks_ctx *c, uint64_t out[8]) {
+  if (!c || !out) return KS_ERR_INVALID;
+  std::memcpy(out, c->cap_ctr, sizeof c->cap_ctr);
+  out[4] = CPB_GROUP;
+  out[5] = (uint64_t)CPB_MAX_BLOCKS * CPB_THREADS;
   return KS_OK;
 }
 

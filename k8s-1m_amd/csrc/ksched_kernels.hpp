@@ -293,6 +293,41 @@ struct DiagPodsArgs {
 // ext: the pods read taint / label / name columns (all of them have PF_EXT, or none)
 hipError_t launch_diagnose_pods(const DiagPodsArgs &a, bool ext, hipStream_t st);
 uint32_t diagnose_pods_blocks(uint32_t npos);  // grid.x of a launch over npos positions
+// ks_capacity (ksched_capacity.hip): the pods [first, first +
+// count) of the call, none with a one-pod program, evaluated in groups of
+// CPB_GROUP on every node row, in launch_diagnose_pods' geometry: recs[i] is
+// pod i's record (zeroed by the caller), cpods[i] its reciprocals; per_node
+// [slots] (null, or zeroed by the caller and count == 1): c of every present
+// node at its slot.
+constexpr int CPB_THREADS = 512;      // lanes of a block, one node position each per grid-stride turn
+constexpr int CPB_GROUP = 64;         // pods per group (grid.y): LDS 64 x 8 counters = 2,048 B
+constexpr int CPB_MAX_BLOCKS = 512;   // grid.x: more positions take further turns of the grid-stride loop
+struct CapPod;
+struct CapRec;
+struct CapPodsArgs {
+  NodeTable t;
+  const uint32_t *pos_slot;   // position -> slot (SLOT_NONE: padding)
+  uint32_t npos;
+  uint32_t first, count;
+  const PodDev *pods;
+  const CapPod *cpods;
+  const uint64_t *clauses;
+  CapRec *recs;
+  uint32_t *per_node;
+};
+// ext: the pods read taint / label / name columns (all of them have PF_EXT, or none)
+hipError_t launch_capacity_pods(const CapPodsArgs &a, bool ext, hipStream_t st);
+uint32_t capacity_pods_blocks(uint32_t npos);  // grid.x of a launch over npos positions
+// the per-pod pass for a.pod, a pod with a one-pod program, in launch_diagnose's
+// place (no prep / min pass: the call refuses what would need one): cpods
+// indexed as a.pods; ports: the pod wants host ports (a.ports_conflict the
+// entries they conflict with now); rec zeroed by the caller
+struct CapPodArgs {
+  CapRec *rec;
+  const CapPod *cpods;
+  uint32_t *per_node;
+};
+hipError_t launch_capacity_pod(const SpreadArgs &a, const CapPodArgs &g, bool ports, hipStream_t st);
 // the chain's front for a.pod without a window: [prep + min], the filter pass
 // launch_spread_pod would choose for `passes`, [score]; the accumulators and
 // the per-position columns (st, part, raw, ipa_raw) stay as the select pass

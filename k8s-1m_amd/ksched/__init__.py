@@ -6,6 +6,7 @@ from . import _abi, objects, synth  # noqa: F401
 from .framework import (  # noqa: F401
     FILTER_PLUGINS,
     NODE_PLUGIN_SCORES_STATE_KEY,
+    Capacity,
     Code,
     CycleState,
     Diagnosis,

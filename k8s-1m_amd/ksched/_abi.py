@@ -356,6 +356,19 @@ class KsExplanation(C.Structure):  # ks_explanation (ks_explain)
                 ("top_score_nodes", C.c_uint32), ("top_score", C.c_int64)]
 
 
+CAP_PODS, CAP_CPU, CAP_MEMORY, CAP_PORTS, CAP_X, CAP_BOUNDS = 0, 1, 2, 3, 4, 12  # KS_CAP_*
+
+
+class KsCapacity(C.Structure):  # ks_capacity (ks_capacity_pod)
+    _fields_ = [("num_all_nodes", C.c_uint32), ("eligible_nodes", C.c_uint32), ("nodes_with_room", C.c_uint32),
+                ("max_per_node", C.c_uint32), ("replicas", C.c_uint64), ("bound_by", C.c_uint32 * CAP_BOUNDS),
+                ("x_names", C.c_char_p * 8)]
+
+
+class KsPodCapacity(C.Structure):  # ks_pod_capacity (ks_capacity_pods)
+    _fields_ = [("status", C.c_int32), ("_pad", C.c_uint32), ("c", KsCapacity)]
+
+
 EXPLAIN_MAX_CANDIDATES = 128  # KS_EXPLAIN_MAX_CANDIDATES
 DIAG_MAX_REASONS = 96 # more rows than a diagnosis can hold: 63 taints, 11 NodeResourcesFit reasons, 12 others
 FIT_MAX_RESOURCES = 8  # extended resources a strategy may list
@@ -390,6 +403,7 @@ KSCHED_SYMBOLS = [
     "ks_diagnose_pods", "ks_debug_diagnose_pods",
     "ks_explain",
     "ks_batch_forget", "ks_debug_forget",
+    "ks_capacity_pod", "ks_capacity_pods", "ks_debug_capacity",
 ]
 KSGATHER_SYMBOLS = [
     "ksg_open", "ksg_close", "ksg_set_members", "ksg_record_and_wait", "ksg_pending", "ksg_fnv1_32", "ksg_target_index",
@@ -480,6 +494,9 @@ def ksched_lib() -> C.CDLL:
     L.ks_diagnose_pods.argtypes = [vp, P(KsPod), C.c_uint32, P(KsPodDiagnosis), P(KsReason), C.c_uint32, P(C.c_uint32)]
     L.ks_debug_diagnose_pods.argtypes = [vp, P(C.c_uint64)]
     L.ks_explain.argtypes = [vp, P(KsPod), C.c_uint32, P(KsExplanation), P(KsCandidate)]
+    L.ks_capacity_pod.argtypes = [vp, P(KsPod), P(KsCapacity), P(C.c_uint32)]
+    L.ks_capacity_pods.argtypes = [vp, P(KsPod), C.c_uint32, P(KsPodCapacity)]
+    L.ks_debug_capacity.argtypes = [vp, P(C.c_uint64)]
     L.ks_fit_error_message.argtypes = [C.c_uint32, C.c_char_p, P(KsReason), C.c_uint32, C.c_char_p, C.c_size_t,
                                        P(C.c_size_t)]
     L.ks_debug_counters.argtypes = [vp, P(C.c_uint64)]

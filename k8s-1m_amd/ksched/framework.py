@@ -85,6 +85,26 @@ class FitDiagnosis:  # what a FitError says: Diagnosis' reasons as a histogram o
     message: str                 # FitError.Error() without the PostFilter part
 
 
+class _NodeCapacity(int):
+    """``Scheduler.capacity``: the context's node capacity (an int, as before),
+    callable as the capacity query ``capacity(pod, per_node=False)``."""
+    query = None
+
+    def __call__(self, pod, per_node: bool = False):
+        return self.query(pod, per_node)
+
+
+@dataclass
+class Capacity:  # how many more replicas of a pod the cluster holds (ks_capacity_pod)
+    num_all_nodes: int
+    eligible_nodes: int          # nodes passing every filter before NodeResourcesFit
+    nodes_with_room: int         # ... of those, the nodes holding at least one more replica
+    max_per_node: int
+    replicas: int                # the sum over the nodes
+    bound_by: Dict[str, int]     # eligible nodes per binding term: "pods", "cpu", "memory", a resource name, "ports"
+    per_node: Optional[object] = None  # numpy uint32 [capacity]: replicas per slot (``per_node=True``)
+
+
 def fit_error_message(num_all_nodes: int, reasons, prefilter_msg: Optional[str] = None) -> str:
     """FitError.Error() of (reason, count) pairs (ks_fit_error_message: pure host code)."""
     lib = _abi.ksched_lib()
@@ -207,7 +227,10 @@ class Scheduler:
         cfg.hard_pod_affinity_weight = hard_pod_affinity_weight
         cfg.percentage_of_nodes_to_score = percentage_of_nodes_to_score
         self.weights = w
-        self.capacity = node_capacity
+        # the node capacity, as it always was (an int: range(s.capacity), ctypes array sizes), which is also the
+        # capacity query: s.capacity(pod, per_node=False)
+        self.capacity = _NodeCapacity(node_capacity)
+        self.capacity.query = self._capacity_of
         self.ctx = C.c_void_p()
         st = self.lib.ks_open(C.byref(cfg), C.byref(self.ctx))
         if st != 0:
@@ -531,6 +554,60 @@ class Scheduler:
         """ks_debug_diagnose_pods: which paths the last ``diagnose_many`` took."""
         out = (C.c_uint64 * 8)()
         self._ok(self.lib.ks_debug_diagnose_pods(self.ctx, out))
+        return [int(v) for v in out]
+
+    @staticmethod
+    def _capacity(c: _abi.KsCapacity, per_node=None) -> Capacity:
+        names = {_abi.CAP_PODS: "pods", _abi.CAP_CPU: "cpu", _abi.CAP_MEMORY: "memory", _abi.CAP_PORTS: "ports"}
+        bound: Dict[str, int] = {}
+        for b in range(_abi.CAP_BOUNDS):
+            if not c.bound_by[b]:
+                continue
+            if b >= _abi.CAP_X:
+                x = c.x_names[b - _abi.CAP_X]
+                name = x.decode() if x else f"x{b - _abi.CAP_X}"
+            else:
+                name = names[b]
+            bound[name] = bound.get(name, 0) + int(c.bound_by[b])
+        return Capacity(int(c.num_all_nodes), int(c.eligible_nodes), int(c.nodes_with_room), int(c.max_per_node),
+                        int(c.replicas), bound, per_node)
+
+    def _capacity_of(self, pod: Pod, per_node: bool = False) -> Capacity:
+        """``Scheduler.capacity(pod, per_node=False)``: how many more replicas
+        of the pod the cluster holds and what runs out first, from one pass on
+        the device against the cache as it is (ks_capacity_pod).  Nothing is
+        committed.  With ``per_node`` the result carries the count of every
+        slot as a numpy uint32 array."""
+        a = Arena()
+        arr, _ = pods_array([pod], a)
+        c = _abi.KsCapacity()
+        pn = None
+        ptr = None
+        if per_node:
+            import numpy as np
+
+            pn = np.zeros(int(self.capacity), dtype=np.uint32)
+            ptr = pn.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._ok(self.lib.ks_capacity_pod(self.ctx, arr, C.byref(c), ptr))
+        return self._capacity(c, pn)
+
+    def capacity_many(self, pods: Sequence[Pod], strict: bool = True) -> List[Optional[Capacity]]:
+        """``capacity`` for a list of pods in one call (ks_capacity_pods), each
+        pod answered on its own (not the joint capacity of the mix).  A pod the
+        library refuses raises KschedError when ``strict``; otherwise its entry
+        is None and the rest are still answered."""
+        a = Arena()
+        arr, n = pods_array(list(pods), a)
+        out = (_abi.KsPodCapacity * max(1, n))()
+        st = self.lib.ks_capacity_pods(self.ctx, arr, n, out)
+        if st != 0 and (strict or not any(out[i].status == st for i in range(n))):
+            self._ok(st)
+        return [None if out[i].status != 0 else self._capacity(out[i].c) for i in range(n)]
+
+    def capacity_counters(self) -> List[int]:
+        """ks_debug_capacity: which paths the last ``capacity`` / ``capacity_many`` took."""
+        out = (C.c_uint64 * 8)()
+        self._ok(self.lib.ks_debug_capacity(self.ctx, out))
         return [int(v) for v in out]
 
     def explain(self, pod: Pod, k: int = 16) -> Explanation:
