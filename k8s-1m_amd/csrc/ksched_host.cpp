@@ -2007,6 +2007,10 @@ uint32_t kernel_npl(const ks_ctx *c, bool ext) {
   return ext ? std::min<uint32_t>(c->npl, c->ext_npl) : c->npl;
 }
 
+Weights weights_of(const ks_config &cfg) {
+  return Weights{cfg.weight_fit, cfg.weight_balanced, cfg.weight_taint, cfg.weight_affinity, cfg.weight_image};
+}
+
 
 // ====================================================== PodTopologySpread
 // Host side of the spread path (ksched_spread.hip): label sets of bound pods,
@@ -3239,8 +3243,7 @@ ks_status enqueue_round(ks_ctx *c, ks_batch *b, uint32_t k, uint32_t end) {
   a.crow = c->d_crow + (size_t)q * c->P * c->K;
   a.cext = c->d_cext + (size_t)q * c->P * c->K;
   a.slot_pos = c->d_slot_pos;
-  a.w = Weights{c->cfg.weight_fit, c->cfg.weight_balanced, c->cfg.weight_taint, c->cfg.weight_affinity,
-                c->cfg.weight_image};
+  a.w = weights_of(c->cfg);
   a.fs = c->fit_params;
   a.fit_general = c->fit_general;
   a.fit_table = c->d_fit_table;
@@ -5015,8 +5018,7 @@ SpreadArgs spread_args(ks_ctx *c) {
   sa.raw = c->d_sraw;
   sa.part = c->d_spart;
   sa.counters = c->d_counters;
-  sa.w = Weights{c->cfg.weight_fit, c->cfg.weight_balanced, c->cfg.weight_taint, c->cfg.weight_affinity,
-                 c->cfg.weight_image};
+  sa.w = weights_of(c->cfg);
   sa.fs = c->fit_params;
   sa.fit_general = c->fit_general;
   sa.fit_table = c->d_fit_table;
@@ -5026,46 +5028,100 @@ SpreadArgs spread_args(ks_ctx *c) {
   return sa;
 }
 
+// One pod (a one-pod-chain descriptor: PF_SOLO, solo_off valid in w) and its
+// program words on the device for a launch of the chain that commits nothing:
+// the call's transfer begun with room for them and `extra` bytes of the
+// caller's, *sa the context's SpreadArgs with pods / clauses / pod /
+// no_commit / ports_conflict set, *hd the program's header.
+ks_status upload_solo_pod(ks_ctx *c, const PodDev &d, const std::vector<uint64_t> &w, size_t extra, SpreadArgs *sa,
+                          const SoloHdr **hd) {
+  ks_status st;
+  const size_t bytes = sizeof(PodDev) + w.size() * 8 + extra + 2048;
+  if ((st = xfer_begin(c, bytes, bytes))) return st;
+  PodDev *d_pod = dscratch<PodDev>(c, 1);
+  uint64_t *d_cl = dscratch<uint64_t>(c, w.size());
+  if ((st = h2d(c, d_pod, &d, sizeof d)) || (st = h2d(c, d_cl, w.data(), w.size() * 8))) return st;
+  *sa = spread_args(c);
+  sa->pods = d_pod;
+  sa->clauses = d_cl;
+  sa->pod = 0;
+  sa->no_commit = 1;
+  *hd = reinterpret_cast<const SoloHdr *>(w.data() + d.solo_off);
+  sa->ports_conflict = (*hd)->ports;  // (the program holds the conflict mask itself: PORTS_DUMP; no commit, ports_add stays 0)
+  return KS_OK;
+}
+
+// One node's row of a score dump: 10 words from the dump kernel, or
+// SPREAD_DUMP_WORDS from the one-pod chain (chain), which has the spread and
+// pod-affinity columns and the total behind them.
+ks_node_score node_score_from(const int32_t *o, bool chain) {
+  ks_node_score s{};
+  s.status = o[0];
+  s.least_allocated = o[1];
+  s.balanced_allocation = o[2];
+  s.taint_raw = o[3];
+  s.taint_score = o[4];
+  s.affinity_raw = o[5];
+  s.affinity_score = o[6];
+  s.image_locality = o[7];
+  if (chain) {
+    s.spread_raw = o[8];
+    s.spread_score = o[9];
+    s.affinity_pod_raw = o[12];
+    s.affinity_pod_score = o[13];
+  }
+  const int32_t *t = o + (chain ? 10 : 8);
+  s.total_score = (int64_t)(((uint64_t)(uint32_t)t[1] << 32) | (uint32_t)t[0]);
+  return s;
+}
+
 // ks_plugin_scores of a pod with spread constraints: the spread chain in dump mode.
 ks_status spread_plugin_scores(ks_ctx *c, const PodDev &d, const ProgBuf &cl, ks_node_score *out) {
   std::vector<int32_t> raw((size_t)c->cap * SPREAD_DUMP_WORDS);
-  const size_t bytes = sizeof(PodDev) + cl.w.size() * 8 + raw.size() * 4 + 2048;
   ks_status st;
-  if ((st = xfer_begin(c, bytes, bytes))) return st;
-  PodDev *d_pod = dscratch<PodDev>(c, 1);
-  uint64_t *d_cl = dscratch<uint64_t>(c, cl.w.size());
+  SpreadArgs sa{};
+  const SoloHdr *hd = nullptr;
+  if ((st = upload_solo_pod(c, d, cl.w, raw.size() * 4, &sa, &hd))) return st;
   int32_t *d_out = dscratch<int32_t>(c, raw.size());
-  if ((st = h2d(c, d_pod, &d, sizeof d)) || (st = h2d(c, d_cl, cl.w.data(), cl.w.size() * 8))) return st;
-  SpreadArgs sa = spread_args(c);
-  sa.pods = d_pod;
-  sa.clauses = d_cl;
-  sa.pod = 0;
   sa.dump = d_out;
-  sa.no_commit = 1;
-  const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + d.solo_off);
-  sa.ports_conflict = hd->ports;  // (a dump's program holds the conflict mask: PORTS_DUMP; no commit, ports_add stays 0)
   HIPC(c, launch_spread_pod(sa, chain_passes(&sa, ba_columns(c), solo_needs(hd)), c->stream));
   if ((st = d2h(c, raw.data(), d_out, raw.size() * 4)) || (st = xfer_sync(c))) return st;
-  for (uint32_t i = 0; i < c->cap; ++i) {
-    const int32_t *o = &raw[(size_t)i * SPREAD_DUMP_WORDS];
-    ks_node_score s{};
-    s.status = o[0];
-    s.least_allocated = o[1];
-    s.balanced_allocation = o[2];
-    s.taint_raw = o[3];
-    s.taint_score = o[4];
-    s.affinity_raw = o[5];
-    s.affinity_score = o[6];
-    s.image_locality = o[7];
-    s.spread_raw = o[8];
-    s.spread_score = o[9];
-    s.total_score = (int64_t)(((uint64_t)(uint32_t)o[11] << 32) | (uint32_t)o[10]);
-    s.affinity_pod_raw = o[12];
-    s.affinity_pod_score = o[13];
-    out[i] = s;
-  }
+  for (uint32_t i = 0; i < c->cap; ++i) out[i] = node_score_from(&raw[(size_t)i * SPREAD_DUMP_WORDS], true);
   return KS_OK;
 }
+
+// compile_for_dump, and compile_force_solo with it when asked, for the
+// compiles of one scope (under c->mu).
+struct DumpCompile {
+  ks_ctx *c;
+  DumpCompile(ks_ctx *ctx, bool force_solo) : c(ctx) { set(true, force_solo); }
+  ~DumpCompile() { set(false, false); }
+  DumpCompile(const DumpCompile &) = delete;
+  void set(bool dump, bool solo) {
+    c->compile_for_dump = dump;
+    c->compile_force_solo = solo;
+  }
+};
+
+// Selector classes created after epoch0 that no prepared batch references: a
+// query call's compile created them, and the call gives them back.
+void drop_classes_since(ks_ctx *c, uint64_t epoch0) {
+  std::lock_guard<std::mutex> g(c->mu);
+  for (int k = 0; k < MAX_CLASSES; ++k) {
+    SpreadClass &sc = c->classes[k];
+    if (!sc.live || sc.born <= epoch0 || sc.refs) continue;
+    c->class_of.erase(sc.canon);
+    sc = SpreadClass();
+  }
+}
+// ... at the end of the scope, whatever happens in it
+struct ClassDrop {
+  ks_ctx *c;
+  uint64_t epoch0;
+  ClassDrop(ks_ctx *ctx, uint64_t e) : c(ctx), epoch0(e) {}
+  ~ClassDrop() { drop_classes_since(c, epoch0); }
+  ClassDrop(const ClassDrop &) = delete;
+};
 
 }  // namespace
 
@@ -5080,9 +5136,10 @@ ks_status ks_plugin_scores(ks_ctx *c, const ks_pod *pod, ks_node_score *out) {
   ks_status st;
   {
     std::unique_lock<std::mutex> g(c->mu);
-    c->compile_for_dump = true;
-    st = compile_batch(c, pod, 1, &d, cl, g, true);
-    c->compile_for_dump = false;
+    {
+      const DumpCompile mode(c, false);
+      st = compile_batch(c, pod, 1, &d, cl, g, true);
+    }
     if (st) return st;
     if ((st = upload_dirty_ext(c, c->xm))) return st;
   }
@@ -5091,8 +5148,7 @@ ks_status ks_plugin_scores(ks_ctx *c, const ks_pod *pod, ks_node_score *out) {
   DumpArgs a{};
   a.t = c->t;
   a.nslots = c->cap;
-  a.w = Weights{c->cfg.weight_fit, c->cfg.weight_balanced, c->cfg.weight_taint, c->cfg.weight_affinity,
-                c->cfg.weight_image};
+  a.w = weights_of(c->cfg);
   a.fs = c->fit_params;
   a.fit_general = c->fit_general;
   a.fit_table = c->d_fit_table;
@@ -5112,136 +5168,8 @@ ks_status ks_plugin_scores(ks_ctx *c, const ks_pod *pod, ks_node_score *out) {
   a.out = d_out;
   HIPC(c, launch_dump(a, c->stream));
   if ((st = d2h(c, raw.data(), d_out, raw.size() * 4)) || (st = xfer_sync(c))) return st;
-  for (uint32_t i = 0; i < c->cap; ++i) {
-    const int32_t *o = &raw[(size_t)i * 10];
-    ks_node_score s{};
-    s.status = o[0];
-    s.least_allocated = o[1];
-    s.balanced_allocation = o[2];
-    s.taint_raw = o[3];
-    s.taint_score = o[4];
-    s.affinity_raw = o[5];
-    s.affinity_score = o[6];
-    s.image_locality = o[7];
-    s.spread_raw = 0;
-    s.spread_score = 0;
-    s.affinity_pod_raw = 0;
-    s.affinity_pod_score = 0;
-    s.total_score = (int64_t)(((uint64_t)(uint32_t)o[9] << 32) | (uint32_t)o[8]);
-    out[i] = s;
-  }
+  for (uint32_t i = 0; i < c->cap; ++i) out[i] = node_score_from(&raw[(size_t)i * 10], false);
   return KS_OK;
-}
-
-// FitError's reasons of one pod (DESIGN.md §5.15): the pod compiled as a
-// one-pod-chain pod whatever its flags, [prep + min], the diagnose pass, and
-// the record turned into reason rows with the context's names.
-ks_status ks_diagnose(ks_ctx *c, const ks_pod *pod, ks_diagnosis *dg, ks_reason *out, uint32_t cap, uint32_t *n) {
-  if (!c || !pod || !dg || !n || (cap && !out)) return KS_ERR_INVALID;
-  if (ks_status dst_ = drain_async(c)) return dst_;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  PodDev d;
-  ProgBuf cl;
-  ks_status st;
-  uint64_t epoch0;
-  uint32_t num_all;
-  {
-    std::unique_lock<std::mutex> g(c->mu);
-    {  // ks_pods_check's verdict on the pod, with its status and text
-      PodDev d0;
-      ProgBuf cl0;
-      if ((st = compile_batch(c, pod, 1, &d0, cl0, g))) {
-        std::string e;
-        {
-          std::lock_guard<std::mutex> ge(c->err_mu);
-          e = "pod 0: " + c->err;
-        }
-        return c->fail(st, "%s", e.c_str());
-      }
-    }
-    epoch0 = c->class_epoch;
-    c->compile_for_dump = c->compile_force_solo = true;  // no host-port triple interned; a program for every pod
-    st = compile_batch(c, pod, 1, &d, cl, g, true);
-    c->compile_for_dump = c->compile_force_solo = false;
-    if (!st) st = upload_dirty_ext(c, c->xm);
-    if (!st && !c->d_diag_rec && !(st = dalloc(c, &c->d_diag_rec, 1))) st = dalloc(c, &c->d_diag_list, c->cap);
-    num_all = c->n_present;
-  }
-  // selector classes the compile created are dropped again below, whatever happens in between
-  auto drop_classes = [&] {
-    std::lock_guard<std::mutex> g(c->mu);
-    for (int k = 0; k < MAX_CLASSES; ++k) {
-      SpreadClass &sc = c->classes[k];
-      if (!sc.live || sc.born <= epoch0 || sc.refs) continue;
-      c->class_of.erase(sc.canon);
-      sc = SpreadClass();
-    }
-  };
-  DiagRec rec{};
-  std::vector<uint32_t> multi;
-  if (!st) st = [&]() -> ks_status {
-    ks_status s;
-    const size_t bytes = sizeof(PodDev) + cl.w.size() * 8 + sizeof(DiagRec) + 2048;
-    if ((s = xfer_begin(c, bytes, bytes))) return s;
-    PodDev *d_pod = dscratch<PodDev>(c, 1);
-    uint64_t *d_cl = dscratch<uint64_t>(c, cl.w.size());
-    if ((s = h2d(c, d_pod, &d, sizeof d)) || (s = h2d(c, d_cl, cl.w.data(), cl.w.size() * 8))) return s;
-    SpreadArgs sa = spread_args(c);
-    sa.pods = d_pod;
-    sa.clauses = d_cl;
-    sa.pod = 0;
-    sa.no_commit = 1;
-    const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + d.solo_off);
-    sa.ports_conflict = hd->ports;  // (the program holds the conflict mask itself: PORTS_DUMP)
-    const DiagArgs ga{c->d_diag_rec, c->d_diag_list, c->cap};
-    HIPC(c, launch_diagnose(sa, ga, solo_needs(hd).passes, c->stream));
-    if ((s = d2h(c, &rec, c->d_diag_rec, sizeof rec)) || (s = xfer_sync(c))) return s;
-    if (rec.n_multi > c->cap) return c->fail(KS_ERR_DEVICE, "diagnose: %u listed nodes for %u slots", rec.n_multi, c->cap);
-    if (!rec.n_multi) return KS_OK;
-    multi.resize(rec.n_multi);  // the list's used prefix alone
-    if ((s = xfer_begin(c, (size_t)rec.n_multi * 4 + 1024, 0)) ||
-        (s = d2h(c, multi.data(), c->d_diag_list, (size_t)rec.n_multi * 4)) || (s = xfer_sync(c)))
-      return s;
-    return KS_OK;
-  }();
-  drop_classes();
-  if (st) return st;
-  DiagNames nm;
-  std::vector<DiagRow> rows;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    // a node with several untolerated taints reports the first in its own taint order
-    for (uint32_t slot : multi) {
-      if (slot >= c->cap) return c->fail(KS_ERR_DEVICE, "diagnose: listed slot %u >= capacity", slot);
-      for (auto &t : c->nodes[slot].hard_taints) {
-        auto it = c->hard_dict.find(TaintKey{t[0], t[1], (int32_t)t[2]});
-        if (it == c->hard_dict.end() || (d.tol_hard >> it->second & 1ull)) continue;
-        rec.taint[it->second]++;
-        break;
-      }
-    }
-    for (size_t b = 0; b < c->hard_list.size() && b < (size_t)DIAG_TAINT_BINS; ++b)
-      nm.taint[b] = diag_taint_reason(c->strs[c->hard_list[b].key], c->strs[c->hard_list[b].value]);
-    for (size_t x = 0; x < c->xres_names.size() && x < 8; ++x) nm.xres[x] = c->strs[c->xres_names[x]];
-  }
-  const bool conflict = d.flags & PF_NA_CONFLICT;
-  diag_rows(rec, nm, conflict, &rows);
-  std::memset(dg, 0, sizeof *dg);
-  diag_counts(rec, dg);
-  dg->num_all_nodes = num_all;
-  dg->n_reasons = *n = (uint32_t)rows.size();
-  c->diag_strs.clear();
-  for (DiagRow &r : rows) c->diag_strs.push_back(std::move(r.reason));
-  c->diag_prefilter = conflict ? REASON_AFFINITY_CONFLICT : "";
-  dg->prefilter_msg = conflict ? c->diag_prefilter.c_str() : nullptr;
-  if (cap < rows.size()) return c->fail(KS_ERR_INVALID, "diagnose: %zu reasons, room for %u", rows.size(), cap);
-  for (size_t i = 0; i < rows.size(); ++i) out[i] = ks_reason{rows[i].plugin, rows[i].count, c->diag_strs[i].c_str()};
-  return KS_OK;
-}
-
-ks_status ks_fit_error_message(uint32_t num_all_nodes, const char *prefilter_msg, const ks_reason *reasons, uint32_t n,
-                               char *buf, size_t cap, size_t *len) {
-  return fit_error_message(num_all_nodes, prefilter_msg, reasons, n, buf, cap, len);
 }
 
 }  // extern "C"
@@ -5253,24 +5181,15 @@ namespace {
 // passes of one call
 constexpr size_t DP_LIST_PER_NODE = 4;
 
-// One pod through ks_diagnose's pass with the whole list, waited for: a pod of
-// ks_diagnose_pods whose multi-taint entries did not fit.  d is a one-pod-chain
-// descriptor (PF_SOLO, solo_off valid in w).
+// One pod through ks_diagnose's pass with the whole list, waited for:
+// ks_diagnose's pod, or a pod of ks_diagnose_pods whose multi-taint entries
+// did not fit.  d is a one-pod-chain descriptor (PF_SOLO, solo_off valid in w).
 ks_status diagnose_pods_rerun(ks_ctx *c, const PodDev &d, const std::vector<uint64_t> &w, DiagRec *rec,
                               std::vector<uint32_t> *multi) {
   ks_status s;
-  const size_t bytes = sizeof(PodDev) + w.size() * 8 + sizeof(DiagRec) + 2048;
-  if ((s = xfer_begin(c, bytes, bytes))) return s;
-  PodDev *d_pod = dscratch<PodDev>(c, 1);
-  uint64_t *d_cl = dscratch<uint64_t>(c, w.size());
-  if ((s = h2d(c, d_pod, &d, sizeof d)) || (s = h2d(c, d_cl, w.data(), w.size() * 8))) return s;
-  SpreadArgs sa = spread_args(c);
-  sa.pods = d_pod;
-  sa.clauses = d_cl;
-  sa.pod = 0;
-  sa.no_commit = 1;
-  const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(w.data() + d.solo_off);
-  sa.ports_conflict = hd->ports;
+  SpreadArgs sa{};
+  const SoloHdr *hd = nullptr;
+  if ((s = upload_solo_pod(c, d, w, sizeof(DiagRec), &sa, &hd))) return s;
   const DiagArgs ga{c->d_diag_rec, c->d_diag_list, c->cap};
   HIPC(c, launch_diagnose(sa, ga, solo_needs(hd).passes, c->stream));
   if ((s = d2h(c, rec, c->d_diag_rec, sizeof *rec)) || (s = xfer_sync(c))) return s;
@@ -5283,10 +5202,11 @@ ks_status diagnose_pods_rerun(ks_ctx *c, const PodDev &d, const std::vector<uint
   return KS_OK;
 }
 
-// The front ks_diagnose_pods and ks_capacity_pods share: ks_pods_check's
-// verdict on each pod, the accepted pods compiled as a batch compiles them (no
-// host-port triple interned), the context's device columns brought up to
-// date, and the distinct compiled pods in launch order.
+// The front the query calls share: ks_pods_check's verdict on each pod, the
+// accepted pods compiled as a batch compiles them (no host-port triple
+// interned) or, for ks_diagnose and ks_explain, their one pod as a
+// one-pod-chain pod whatever its flags, the context's device columns brought
+// up to date, and the distinct compiled pods in launch order.
 constexpr uint32_t POD_REFUSED = 0xFFFFFFFFu;
 struct PodsFront {
   uint32_t first_idx = POD_REFUSED;  // the first refused pod, its status and text
@@ -5314,9 +5234,10 @@ struct PodsFront {
 
 // verdict(i, status): pod i's entry of the call's output (zeroed, with the
 // status); locked(): the call's own allocations and reads under the context's
-// lock, after the compile and the uploads.
+// lock, after the compile and the uploads; force_solo: a one-pod program for
+// every pod.
 ks_status pods_front_compile(ks_ctx *c, const ks_pod *pods, uint32_t n, const std::function<void(uint32_t, ks_status)> &verdict,
-                             const std::function<ks_status()> &locked, PodsFront *f) {
+                             const std::function<ks_status()> &locked, PodsFront *f, bool force_solo = false) {
   ks_status st = KS_OK;
   std::unique_lock<std::mutex> g(c->mu);
   for (uint32_t i = 0; i < n; ++i) {  // ks_pods_check's verdict on each pod, with its status and text
@@ -5336,26 +5257,16 @@ ks_status pods_front_compile(ks_ctx *c, const ks_pod *pods, uint32_t n, const st
   f->dev.resize(std::max<size_t>(f->acc.size(), 1));
   f->tag.assign(f->acc.size(), 0);
   if (!f->acc.empty()) {
-    c->compile_for_dump = true;  // no host-port triple interned
-    st = compile_batch(c, f->acc.data(), (uint32_t)f->acc.size(), f->dev.data(), f->cl, g, true);
-    c->compile_for_dump = false;
+    {
+      const DumpCompile mode(c, force_solo);  // no host-port triple interned
+      st = compile_batch(c, f->acc.data(), (uint32_t)f->acc.size(), f->dev.data(), f->cl, g, true);
+    }
     if (!st) st = upload_dirty_ext(c, c->xm);
     if (!st) st = spread_alloc(c);  // the position -> slot column
     if (!st) st = locked();
   }
   f->num_all = c->n_present;
   return st;
-}
-
-// selector classes the compile created are dropped again, whatever happened in between
-void pods_front_drop(ks_ctx *c, const PodsFront &f) {
-  std::lock_guard<std::mutex> g(c->mu);
-  for (int k = 0; k < MAX_CLASSES; ++k) {
-    SpreadClass &sc = c->classes[k];
-    if (!sc.live || sc.born <= f.epoch0 || sc.refs) continue;
-    c->class_of.erase(sc.canon);
-    sc = SpreadClass();
-  }
 }
 
 // identical compiled pods (descriptor, program words and tag) are answered once: rep[j] the first of j's class
@@ -5402,6 +5313,70 @@ void pods_front_classes(PodsFront *f) {
 
 extern "C" {
 
+// FitError's reasons of one pod (DESIGN.md §5.15): the pod compiled as a
+// one-pod-chain pod whatever its flags, [prep + min], the diagnose pass, and
+// the record turned into reason rows with the context's names.
+ks_status ks_diagnose(ks_ctx *c, const ks_pod *pod, ks_diagnosis *dg, ks_reason *out, uint32_t cap, uint32_t *n) {
+  if (!c || !pod || !dg || !n || (cap && !out)) return KS_ERR_INVALID;
+  if (ks_status dst_ = drain_async(c)) return dst_;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  PodsFront f;
+  ks_status st = pods_front_compile(
+      c, pod, 1, [](uint32_t, ks_status) {},
+      [&]() -> ks_status {
+        ks_status s = KS_OK;
+        if (!c->d_diag_rec && !(s = dalloc(c, &c->d_diag_rec, 1))) s = dalloc(c, &c->d_diag_list, c->cap);
+        return s;
+      },
+      &f, true);
+  if (f.first) return c->fail(f.first, "%s", f.first_err.c_str());
+  const PodDev &d = f.dev[0];
+  const uint32_t num_all = f.num_all;
+  DiagRec rec{};
+  std::vector<uint32_t> multi;
+  {
+    const ClassDrop drop(c, f.epoch0);  // the selector classes the compile created, whatever happens in between
+    if (!st) st = diagnose_pods_rerun(c, d, f.cl.w, &rec, &multi);
+  }
+  if (st) return st;
+  DiagNames nm;
+  std::vector<DiagRow> rows;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    // a node with several untolerated taints reports the first in its own taint order
+    for (uint32_t slot : multi) {
+      if (slot >= c->cap) return c->fail(KS_ERR_DEVICE, "diagnose: listed slot %u >= capacity", slot);
+      for (auto &t : c->nodes[slot].hard_taints) {
+        auto it = c->hard_dict.find(TaintKey{t[0], t[1], (int32_t)t[2]});
+        if (it == c->hard_dict.end() || (d.tol_hard >> it->second & 1ull)) continue;
+        rec.taint[it->second]++;
+        break;
+      }
+    }
+    for (size_t b = 0; b < c->hard_list.size() && b < (size_t)DIAG_TAINT_BINS; ++b)
+      nm.taint[b] = diag_taint_reason(c->strs[c->hard_list[b].key], c->strs[c->hard_list[b].value]);
+    for (size_t x = 0; x < c->xres_names.size() && x < 8; ++x) nm.xres[x] = c->strs[c->xres_names[x]];
+  }
+  const bool conflict = d.flags & PF_NA_CONFLICT;
+  diag_rows(rec, nm, conflict, &rows);
+  std::memset(dg, 0, sizeof *dg);
+  diag_counts(rec, dg);
+  dg->num_all_nodes = num_all;
+  dg->n_reasons = *n = (uint32_t)rows.size();
+  c->diag_strs.clear();
+  for (DiagRow &r : rows) c->diag_strs.push_back(std::move(r.reason));
+  c->diag_prefilter = conflict ? REASON_AFFINITY_CONFLICT : "";
+  dg->prefilter_msg = conflict ? c->diag_prefilter.c_str() : nullptr;
+  if (cap < rows.size()) return c->fail(KS_ERR_INVALID, "diagnose: %zu reasons, room for %u", rows.size(), cap);
+  for (size_t i = 0; i < rows.size(); ++i) out[i] = ks_reason{rows[i].plugin, rows[i].count, c->diag_strs[i].c_str()};
+  return KS_OK;
+}
+
+ks_status ks_fit_error_message(uint32_t num_all_nodes, const char *prefilter_msg, const ks_reason *reasons, uint32_t n,
+                               char *buf, size_t cap, size_t *len) {
+  return fit_error_message(num_all_nodes, prefilter_msg, reasons, n, buf, cap, len);
+}
+
 // FitError's reasons of a list of pods: the accepted pods
 // compiled as a batch compiles them, byte-identical ones diagnosed once; pods
 // without a one-pod program evaluated in groups on every node row
@@ -5439,7 +5414,6 @@ ks_status ks_diagnose_pods(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_pod_dia
       nm.taint[b] = diag_taint_reason(c->strs[c->hard_list[b].key], c->strs[c->hard_list[b].value]);
     for (size_t x = 0; x < c->xres_names.size() && x < 8; ++x) nm.xres[x] = c->strs[c->xres_names[x]];
   }
-  auto drop_classes = [&] { pods_front_drop(c, f); };
   const ks_status first = f.first;
   const std::string &first_err = f.first_err;
   const std::vector<uint32_t> &acc_of = f.acc_of;
@@ -5464,7 +5438,9 @@ ks_status ks_diagnose_pods(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_pod_dia
   const size_t list_cap = DP_LIST_PER_NODE * c->cap;
   const uint32_t share = n_solo ? (uint32_t)std::min<size_t>(c->cap, list_cap / n_solo) : 0;
   std::vector<uint32_t> again;  // pods whose listed entries did not all fit
-  if (!st && D) st = [&]() -> ks_status {
+  st = [&]() -> ks_status {
+    const ClassDrop drop(c, f.epoch0);  // the selector classes the compile created, whatever happens in between
+    if (st || !D) return st;
     ks_status s;
     std::vector<PodDev> hp(D);
     for (uint32_t k = 0; k < D; ++k) hp[k] = dev[order[k]];
@@ -5547,7 +5523,6 @@ ks_status ks_diagnose_pods(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_pod_dia
     }
     return KS_OK;
   }();
-  if (m) drop_classes();
   if (st) return st;
   c->dp_ctr[0] = n_plain + n_ext;
   c->dp_ctr[1] = n_solo;
@@ -5680,7 +5655,9 @@ ks_status capacity_run(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_pod_capacit
   const uint32_t D = (uint32_t)f.order.size(), n_plain = f.n_plain, n_ext = f.n_ext;
   std::vector<CapRec> recs(D);
   std::vector<uint32_t> cols(D, 0);  // extended-resource columns each distinct pod requests
-  if (!st && D) st = [&]() -> ks_status {
+  st = [&]() -> ks_status {
+    const ClassDrop drop(c, f.epoch0);  // the selector classes the compile created, whatever happens in between
+    if (st || !D) return st;
     ks_status s;
     std::vector<PodDev> hp(D);
     std::vector<CapPod> cp(D);
@@ -5746,7 +5723,6 @@ ks_status capacity_run(ks_ctx *c, const ks_pod *pods, uint32_t n, ks_pod_capacit
       return s;
     return KS_OK;
   }();
-  if (m) pods_front_drop(c, f);
   if (st) return st;
   c->cap_ctr[0] = n_plain + n_ext;
   c->cap_ctr[1] = f.n_solo;
@@ -5805,65 +5781,28 @@ ks_status ks_explain(ks_ctx *c, const ks_pod *pod, uint32_t k, ks_explanation *e
   if (!c || !pod || !ex || !out || !k || k > KS_EXPLAIN_MAX_CANDIDATES) return KS_ERR_INVALID;
   if (ks_status dst_ = drain_async(c)) return dst_;
   HIPC(c, hipSetDevice(c->cfg.device));
-  PodDev d;
-  ProgBuf cl;
-  ks_status st;
-  uint64_t epoch0;
-  uint32_t num_all;
-  {
-    std::unique_lock<std::mutex> g(c->mu);
-    {  // ks_pods_check's verdict on the pod, with its status and text
-      PodDev d0;
-      ProgBuf cl0;
-      if ((st = compile_batch(c, pod, 1, &d0, cl0, g))) {
-        std::string e;
-        {
-          std::lock_guard<std::mutex> ge(c->err_mu);
-          e = "pod 0: " + c->err;
-        }
-        return c->fail(st, "%s", e.c_str());
-      }
-    }
-    epoch0 = c->class_epoch;
-    c->compile_for_dump = c->compile_force_solo = true;  // no host-port triple interned; a program for every pod
-    st = compile_batch(c, pod, 1, &d, cl, g, true);
-    c->compile_for_dump = c->compile_force_solo = false;
-    if (!st) st = upload_dirty_ext(c, c->xm);
-    if (!st && !c->d_explain) st = dalloc(c, &c->d_explain, 1);
-    num_all = c->n_present;
-  }
+  PodsFront f;
+  ks_status st = pods_front_compile(
+      c, pod, 1, [](uint32_t, ks_status) {}, [&]() -> ks_status { return c->d_explain ? KS_OK : dalloc(c, &c->d_explain, 1); },
+      &f, true);
+  if (f.first) return c->fail(f.first, "%s", f.first_err.c_str());
+  const uint32_t num_all = f.num_all;
   ExplainOut got;
-  if (!st) st = [&]() -> ks_status {
+  st = [&]() -> ks_status {
+    const ClassDrop drop(c, f.epoch0);  // the selector classes the compile created, whatever happens in between
+    if (st) return st;
     ks_status s;
     const size_t back = sizeof(ExplainRec) + (size_t)k * sizeof(ks_candidate);
-    const size_t bytes = sizeof(PodDev) + cl.w.size() * 8 + back + 2048;
-    if ((s = xfer_begin(c, bytes, bytes))) return s;
-    PodDev *d_pod = dscratch<PodDev>(c, 1);
-    uint64_t *d_cl = dscratch<uint64_t>(c, cl.w.size());
-    if ((s = h2d(c, d_pod, &d, sizeof d)) || (s = h2d(c, d_cl, cl.w.data(), cl.w.size() * 8))) return s;
-    SpreadArgs sa = spread_args(c);
-    sa.pods = d_pod;
-    sa.clauses = d_cl;
-    sa.pod = 0;
-    sa.no_commit = 1;
+    SpreadArgs sa{};
+    const SoloHdr *hd = nullptr;
+    if ((s = upload_solo_pod(c, f.dev[0], f.cl.w, back, &sa, &hd))) return s;
     sa.nslots = c->cap;
-    const SoloHdr *hd = reinterpret_cast<const SoloHdr *>(cl.w.data() + d.solo_off);
-    sa.ports_conflict = hd->ports;  // (the program holds the conflict mask itself: PORTS_DUMP)
     ks_ctx::ExplainDev *dv = c->d_explain;
     const ExplainArgs xa{&dv->blk_keys[0][0], dv->blk_best, dv->keys, &dv->out, k};
     HIPC(c, launch_explain(sa, xa, chain_passes(&sa, ba_columns(c), solo_needs(hd)), c->stream));
     if ((s = d2h(c, &got, &dv->out, back)) || (s = xfer_sync(c))) return s;
     return KS_OK;
   }();
-  {  // selector classes the compile created are dropped again, whatever happened in between
-    std::lock_guard<std::mutex> g(c->mu);
-    for (int q = 0; q < MAX_CLASSES; ++q) {
-      SpreadClass &sc = c->classes[q];
-      if (!sc.live || sc.born <= epoch0 || sc.refs) continue;
-      c->class_of.erase(sc.canon);
-      sc = SpreadClass();
-    }
-  }
   if (st) return st;
   if (got.rec.n_candidates > k) return c->fail(KS_ERR_DEVICE, "explain: %u candidates for k %u", got.rec.n_candidates, k);
   std::memset(ex, 0, sizeof *ex);
